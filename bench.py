@@ -12,7 +12,13 @@ ranks denoised / max-over-ranks wall time.  Inputs (weights, x_T, text embedding
 HBM before the timed region; per-step noise is generated in the fused step kernel (Philox), as the reference draws
 randn_like on the device inside its loop.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K passes and prints the JSON line (`metric`, `value`, `unit`, `ms_per_step` = wall ms
+of one timed pass, `higher_is_better`, `dtype`, the workload's `config`).  --dump-outputs DIR writes, after the timed passes,
+what the last timed pass returned (the denoised clips) as DIR/<name>.npy; the inputs depend on the arguments only, so two
+builds compare output for output.
+
+--full adds what the headline does not need, with runs of its own or instruments inside the timed region; the line then
+also carries
   roofline      the dominant kernel by device time PER ROCPROF SYMBOL (out-proj and FFN2 launches are one symbol, the
                 LayerNorm-epilogue GEMM): algorithmic FLOPs per launch / average launch duration measured with HIP
                 events on the launch stream inside the timed region (every 50th denoise step is instrumented), against
@@ -23,11 +29,13 @@ The JSON line also carries
                 engine-level `value`.
   cpu_baseline  the CPU oracle (a port of the reference's fp32 path; oracle/) timed on this box's host cores on a
                 bounded sample of the same workload (rank 0, N = 1 only).
+and the last pass is checked: finite, and the inpainted rows equal to the content clip.
 
 --mode finetune.  BASELINE.json configs[3]: one step = one data-parallel fine-tune iteration
 (`few_shot_style_finetune_losses`, DDIM-20 / skip 700, 64 text-to-motion clips per rank + the single-clip style branch,
 backward, per-layer bucketed gradient all-reduce over RCCL overlapped with the backward pass, AdamW);
-value = text-to-motion clips all ranks trained on / max-over-ranks wall time.
+value = text-to-motion clips all ranks trained on / max-over-ranks wall time.  --dump-outputs writes the last timed
+iteration's loss and a fixed sample of the updated trainable parameters.
 """
 import argparse
 import json
@@ -102,7 +110,34 @@ def parse():
     ap.add_argument("--shared-device", action="store_true",
                     help="rehearsal on a 1-GPU box: every rank uses cuda:0 (use with --backend gloo)")
     ap.add_argument("--cpu-sample-steps", type=int, default=24)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="sample mode: also the roofline (event-timed launches inside the timed region), the via-boundary legs, "
+                         "the CPU baseline and the output checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: one DIR/<name>.npy per array (float32; float64 stays float64), `budget` bytes in all.  An array over its
+    share is written as a fixed sample of its elements (flat indices from a seeded generator, sorted), the same in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def spawn_ranks(args):
@@ -195,9 +230,10 @@ def sample_main(args):
     motion = to(syn.normal(seed + rank, "bench/motion", (B, F, 1, T)))
     mask = to(syn.root_horizontal_mask(B, F, T))
     scale = to(np.full((B,), 2.5, np.float32)) if args.cfg else None
+    torch.manual_seed(seed + rank)          # the drop-in call draws its noise (or Philox key) from torch's generators
 
     model = diffusion = None
-    if args.via_boundary or not args.no_boundary:
+    if args.via_boundary or (args.full and not args.no_boundary):
         model, diffusion = build_boundary(seed, F, w, dev)
         if args.cfg:
             from mst_amd.model.cfg_sampler import ClassifierFreeSampleModel
@@ -232,7 +268,8 @@ def sample_main(args):
     barrier = lambda: sharding.barrier(dev)
     for k in range(args.warmup):
         one_pass(k)
-    if eng is not None:
+    profiled = eng is not None and args.full
+    if profiled:
         eng.profile(True, 50)
     barrier()
     t0 = time.perf_counter()
@@ -242,17 +279,20 @@ def sample_main(args):
     barrier()
     dt = time.perf_counter() - t0
     prof, ev_us = {}, 0.0
-    if eng is not None:
+    if profiled:
         prof = eng.profile_read()
         ev_us = max(0.0, eng.profile_event_overhead_us())
         eng.profile(False)
-    assert torch.isfinite(last).all()
-    assert torch.equal(last[:, :3], motion[:, :3]), "inpainted rows must equal the content clip exactly"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"sample" if world == 1 else f"sample_rank{rank}": last}, DUMP_BYTES // world)
+    if args.full:
+        assert torch.isfinite(last).all()
+        assert torch.equal(last[:, :3], motion[:, :3]), "inpainted rows must equal the content clip exactly"
     group = sharding.group_report(dt, B * args.steps, dev if args.backend == "nccl" else "cpu")      # before the max: every rank's OWN time
     dt = sharding.max_over_ranks(dt, dev if args.backend == "nccl" else "cpu")
 
     boundary = None
-    if rank == 0 and world == 1 and not args.via_boundary and not args.no_boundary:
+    if rank == 0 and world == 1 and args.full and not args.via_boundary and not args.no_boundary:
         boundary = {"call": "diffusion.p_sample_loop(model, (B,263,1,196), noise=x_T, clip_denoised=False, model_kwargs={'y': ...})"}
         with torch.no_grad():                                # one model call first: the module builds its engine and uploads its weights there (one-time set-up,
             model(x_T, torch.zeros(B, dtype=torch.long, device=dev),      # not part of a loop's rate)
@@ -284,15 +324,15 @@ def sample_main(args):
                        "global_batch": world * B, "denoise_steps": NS, "parallelism": f"clip-sharded x{world}, no collective"},
         }
         line["distributed"] = group
-        if eng is not None:
+        if profiled:
             line["roofline"] = roofline(prof, rows, B, T, F, value, flops_per_clip, eng.loop_slices(B, args.cfg), ev_us)
-        else:
+        elif args.full:
             line["roofline"] = {"bound": "mfma", "achieved": round(value * flops_per_clip * 1e-12, 2), "peak": MFMA_PEAK_TFLOPS,
                                 "unit": "TFLOP/s", "frac": round(value * flops_per_clip * 1e-12 / MFMA_PEAK_TFLOPS, 4),
                                 "traffic": None, "kernel": "whole path (no per-kernel events through the boundary)"}
         if boundary is not None:
             line["boundary"] = boundary
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(w, pe, tab, tmap, B, F, T, NS, args.cpu_sample_steps, seed)
         print(json.dumps(line), flush=True)
     if dist is not None:
@@ -516,6 +556,7 @@ def finetune_main(args):
 
     world, rank, dev, dist = init_dist(args)
     B, F, T, seed = args.batch, 263, 196, 20261003
+    torch.manual_seed(seed + rank)          # the objective's noise, condition drop and dropout keys come from torch's generators
     a = types.SimpleNamespace(dataset="humanml", latent_dim=512, layers=8, cond_mask_prob=0.1, arch="trans_enc",
                               emb_trans_dec=False, diffusion_steps=1000, noise_schedule="cosine", sigma_small=True,
                               lambda_vel=0.0, lambda_rcxyz=0.0, lambda_fc=0.0)
@@ -570,6 +611,10 @@ def finetune_main(args):
         iteration()
     dt, loss = timed(args.steps)
     host_s = timed.host_s
+    if args.dump_outputs:
+        sfx = "" if world == 1 else f"_rank{rank}"
+        params = torch.cat([p.detach().float().reshape(-1) for p in model.parameters_wo_enc()])
+        dump_outputs(args.dump_outputs, {"loss" + sfx: np.float32(loss), "trainable_params" + sfx: params}, DUMP_BYTES // world)
     group = sharding.group_report(dt, B * args.steps, dev if args.backend == "nccl" else "cpu")
     dt = sharding.max_over_ranks(dt, dev if args.backend == "nccl" else "cpu")
     comm = None

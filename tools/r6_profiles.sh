@@ -11,7 +11,7 @@ MST_STREAMS=1 MST_FUSE_EMBED=0 timeout -k 10 300 rocprofv3 --kernel-trace --pmc 
 python3 tools/pmc_traffic.py $O/pmcF $O/pmcW > $O/r06_pmc_traffic.json; head -30 $O/r06_pmc_traffic.json
 cp $O/r06_pmc_traffic.json profiles/r06_pmc_traffic.json
 find $O/pmc?* -name "*kernel_trace.csv" -delete
-step "bench default";  timeout -k 10 600 python bench.py > $O/bench_default.log 2>&1 || exit 1; tail -1 $O/bench_default.log > $O/r06_bench_default.json; cut -c1-400 $O/r06_bench_default.json
+step "bench default";  timeout -k 10 600 python bench.py --full > $O/bench_default.log 2>&1 || exit 1; tail -1 $O/bench_default.log > $O/r06_bench_default.json; cut -c1-400 $O/r06_bench_default.json
 step "bench, driver form"; timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $O/bench_driver.log 2>&1 || exit 1; tail -1 $O/bench_driver.log > $O/r06_bench_driver_form_steps20.json; cut -c1-200 $O/r06_bench_driver_form_steps20.json
 step "bench cfg";      timeout -k 10 300 python bench.py --cfg --steps 2 --warmup 1 --no-cpu-baseline --no-boundary > $O/bench_cfg.log 2>&1 || exit 1; tail -1 $O/bench_cfg.log > $O/r06_bench_cfg.json; cut -c1-200 $O/r06_bench_cfg.json
 step "bench batch 128"; timeout -k 10 300 python bench.py --batch 128 --steps 2 --warmup 1 --no-cpu-baseline --no-boundary > $O/bench_b128.log 2>&1 || exit 1; tail -1 $O/bench_b128.log > $O/r06_bench_batch128.json; cut -c1-200 $O/r06_bench_batch128.json
