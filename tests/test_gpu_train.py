@@ -50,7 +50,7 @@ def tile_path(request, monkeypatch):
 def engine_for(tag, max_rows=4):
     import os
     from mst_amd.engine import DenoiserEngine
-    tag_key = (tag, os.environ.get("MST_SMALL_M"))
+    tag_key = (tag,) + tuple(os.environ.get(k) for k in ("MST_SMALL_M", "MST_TRAIN_FUSE_BWD_TAIL", "MST_TRAIN_FUSE_LN2_BWD"))
     if tag_key not in _ENGINES:
         Fe, T = SHAPES[tag]
         eng = DenoiserEngine(Fe, T, max_rows, device=_dev())
@@ -70,17 +70,24 @@ def layer_params(w, requires_grad):
     return out
 
 
-def torch_stack(h, params, masks=None):
-    """Eight post-norm encoder layers in fp32; h: [B, S, 512].  masks[l] = (m0 [B,4,S,S], m1 [B,S,512],
-    m2 [B,S,1024], m3 [B,S,512]) keep-multipliers or None."""
+def torch_stack(h, params, masks=None, keep=None):
+    """Eight post-norm encoder layers in the precision of h and params (fp32 here, fp64 in test_gpu_train_shapes.py); h: [B, S, 512].
+    masks[l] = (m0 [B,4,S,S], m1 [B,S,512], m2 [B,S,1024], m3 [B,S,512]) keep-multipliers or None.  keep: optional [B, S] bool,
+    False = padding key (src_key_padding_mask inverted), applied as an additive -inf bias on the attention scores."""
     B, S, _ = h.shape
     x = h
+    bias = None
+    if keep is not None:
+        bias = torch.zeros(keep.shape, dtype=h.dtype, device=h.device).masked_fill(~keep.bool(), float("-inf"))[:, None, None, :]
     for l in range(L):
         win, bin_, wout, bout, w1, b1, w2, b2, g1, be1, g2, be2 = params[12 * l:12 * l + 12]
         m = masks[l] if masks is not None else (None,) * 4
         qkv = x @ win.t() + bin_
         q, k, v = qkv.view(B, S, 3, H, D // H).permute(2, 0, 3, 1, 4)          # [B, H, S, hd]
-        p = torch.softmax((q * (D // H) ** -0.5) @ k.transpose(-1, -2), dim=-1)
+        s = (q * (D // H) ** -0.5) @ k.transpose(-1, -2)
+        if bias is not None:
+            s = s + bias
+        p = torch.softmax(s, dim=-1)
         if m[0] is not None:
             p = p * m[0]
         att = (p @ v).permute(0, 2, 1, 3).reshape(B, S, D)
@@ -331,9 +338,10 @@ def test_motion_encoder_masked_stack_native_vs_torch_ops():
 
 
 @pytest.mark.parametrize("rows,S,p", [(1, 2, 0.0), (1, 33, 0.3), (4, 64, 0.0), (2, 77, 0.5)])
-def test_train_edge_shapes(rows, S, p):
+def test_train_edge_shapes(rows, S, p, tile_path, monkeypatch):
     """Smallest sequence (2 tokens), tile-boundary lengths (33, 64), one clip, heavy dropout: forward, input gradient and a
-    few parameter gradients against fp32 autograd with the engine's masks; frozen mode (grads=None) returns the same dL/dh."""
+    few parameter gradients against fp32 autograd with the engine's masks; frozen mode (grads=None) returns the same dL/dh, to 1e-6
+    where both passes take the same kernels."""
     eng, w = engine_for("xia")
     h = torch.from_numpy(syn.normal(SEED, f"edge/h/{rows}/{S}", (rows, S, D))).to(_dev())
     r = torch.from_numpy(syn.normal(SEED, f"edge/r/{rows}/{S}", (rows, S, D))).to(_dev())
@@ -356,6 +364,25 @@ def test_train_edge_shapes(rows, S, p):
     d_in2 = eng.train_backward(tape, r, p, seed, None)
     assert rel_l2(d_in2.cpu().numpy(), href.grad.cpu().numpy()) <= TOL_GRAD
     assert rel_l2(d_in2.cpu().numpy(), d_in.cpu().numpy()) < 1.5e-3
+    # like with like: the two passes agree to 1e-6 when they take the same kernels.  The small-tile path always does; on the large-tile
+    # path, engines with both passes unfused (MST_TRAIN_FUSE_BWD_TAIL=0) and both fused (=2; LayerNorm2 in its own launch, as the pass
+    # with parameter gradients has it: MST_TRAIN_FUSE_LN2_BWD=0), both read when the engine is created
+    if tile_path != "0":
+        assert rel_l2(d_in2.cpu().numpy(), d_in.cpu().numpy()) < 1e-6
+        return
+    for fuse in ("0", "2"):
+        monkeypatch.setenv("MST_TRAIN_FUSE_BWD_TAIL", fuse)
+        monkeypatch.setenv("MST_TRAIN_FUSE_LN2_BWD", "0")
+        e, _ = engine_for("xia")
+        monkeypatch.delenv("MST_TRAIN_FUSE_BWD_TAIL")
+        monkeypatch.delenv("MST_TRAIN_FUSE_LN2_BWD")
+        out_v, tape_v = e.train_forward(h, p, seed)
+        assert torch.equal(out_v, out), fuse
+        g_v = [torch.zeros_like(q) for q in params]
+        d_wg = e.train_backward(tape_v, r, p, seed, g_v)
+        d_fz = e.train_backward(tape_v, r, p, seed, None)
+        assert rel_l2(d_wg.cpu().numpy(), href.grad.cpu().numpy()) <= TOL_GRAD, fuse
+        assert rel_l2(d_fz.cpu().numpy(), d_wg.cpu().numpy()) < 1e-6, fuse
 
 
 @pytest.mark.parametrize("rows,p", [(14, 0.1), (20, 0.1)])
