@@ -92,6 +92,10 @@ SIGNATURES = {
     "mst_trunk_check": (C.c_int, [C.c_void_p]),
     "mst_debug_stop_after": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "mst_debug_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mst_style_slots": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mst_load_layers_slot": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p]),
+    "mst_set_styles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mst_plan_style_segments": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
 }
 
 

@@ -130,14 +130,12 @@ __global__ __launch_bounds__(256) void k_rowwise_linear(const float* __restrict_
 // Small launches: y = LayerNorm(acc + bias + residual) for rows of 512, one wave per row; the stream (hi/lo pair) is
 // read as the residual and rewritten in place.  `acc` is the fp32 GEMM result of a launch tiled over N (k_gemm_dma with
 // 64 x 128 tiles + DEpiPlainF32) -- the fused whole-row epilogue would leave all but 4 CUs idle at one clip.
-__global__ __launch_bounds__(256) void k_ln_rows(const float* __restrict__ acc, const float* __restrict__ bias,
-                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                 f16* hi, f16* lo, int M, f16* ohi = nullptr, f16* olo = nullptr) {
-    // (ohi, olo): the normalised rows go there instead of over the residual (the last LayerNorm of a stack whose other LayerNorms ran
-    // inside the GEMM behind them, mst_small.h: its residual sits in the second stream buffer, its consumer reads the first)
-    if (!ohi) { ohi = hi; olo = lo; }
-    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
+// one wave per token row; (ohi, olo): the normalised rows go there instead of over the residual (the last LayerNorm of a stack whose other
+// LayerNorms ran inside the GEMM behind them, mst_small.h: its residual sits in the second stream buffer, its consumer reads the first)
+__device__ __forceinline__ void ln_rows_body(const float* __restrict__ acc, const float* __restrict__ bias,
+                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+                                             f16* hi, f16* lo, f16* ohi, f16* olo, int row) {
+    const int lane = threadIdx.x & 63;
     const int fa = lane * 4, fb = 256 + lane * 4;
     const size_t off = (size_t)row * MST_D;
     f32x4 xa = join4_f16(*reinterpret_cast<const uint2*>(hi + off + fa), *reinterpret_cast<const uint2*>(lo + off + fa));
@@ -160,6 +158,14 @@ __global__ __launch_bounds__(256) void k_ln_rows(const float* __restrict__ acc, 
     split4_f16(yb, h, l);
     *reinterpret_cast<uint2*>(ohi + off + fb) = h;
     *reinterpret_cast<uint2*>(olo + off + fb) = l;
+}
+__global__ __launch_bounds__(256) void k_ln_rows(const float* __restrict__ acc, const float* __restrict__ bias,
+                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                 f16* hi, f16* lo, int M, f16* ohi = nullptr, f16* olo = nullptr) {
+    if (!ohi) { ohi = hi; olo = lo; }
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    ln_rows_body(acc, bias, gamma, beta, hi, lo, ohi, olo, row);
 }
 
 // debug / tests: the stream as float32

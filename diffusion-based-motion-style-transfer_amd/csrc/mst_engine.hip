@@ -28,6 +28,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #endif
 #include "mst_embed.h"
 #include "mst_small.h"
+#include "mst_style.h"
 
 using namespace mst;
 
@@ -173,6 +174,10 @@ static const char* kFamilyNames[FAM_COUNT] = {"cond_token", "embed_in", "qkv_gem
 
 struct ProfPoint { int fam; hipEvent_t a, b; };
 
+// Several styles in one batch (mst_style_slots / mst_set_styles; csrc/mst_style.h).  Where one slice of a call finds its tables inside
+// the engine's plan buffer (int offsets; segments per tile height 16, 32, 48, 64 rows).
+struct StyleSlice { int rows = 0, off_slot = 0, off_order = 0, off_seg[4] = {0, 0, 0, 0}, nseg[4] = {0, 0, 0, 0}; };
+
 struct mst_engine {
     mst_config cfg;
     int S_max = 0, M_pad = 0, kin_pad = 0, nt_out = 0, fout_pad = 0;
@@ -264,6 +269,20 @@ struct mst_engine {
     float prof_overhead_us = -1.f;        // median duration an empty event pair reports (calibrated at mst_profile_enable)
     double prof_ms[FAM_COUNT] = {0};
     int prof_n[FAM_COUNT] = {0};
+    // several styles (mst_style.h): slot 0 is L[]; slots 1 .. nslots - 1 hold only what sampling reads
+    int nslots = 1;
+    std::vector<LayerW> slot_w;           // [(slot - 1) * 16 + layer]
+    StyleLayer* style_tab = nullptr;      // [nslots][num_layers] in device memory (pointers fixed when the slots are made)
+    f16* style_stage = nullptr;           // one layer's plain f16 matrices: mst_load_layers_slot converts into it, then packs
+    std::vector<int> styles;              // slot of every clip of the batch mst_set_styles named (empty: off)
+    int style_xcd = 1;                    // segments and clips ordered so that one style's workgroups share XCDs (MST_STYLE_XCD=0: plain order;
+                                          // same box, 8 styles x 8 HumanML clips: 87.6 against 85.0 clips/s, profiles/style_bank_bench.txt)
+    int* plan_dev = nullptr;              // this call's tables (row slots, clip order, segments), ONE upload per call
+    size_t plan_cap = 0;
+    std::vector<int> plan_host;
+    hipEvent_t plan_ev = nullptr;         // recorded behind the upload: plan_host is not rewritten before the copy has read it
+    StyleSlice plan_sl[MAX_SLICES];
+    const StyleSlice* style_cur = nullptr;   // the slice run_trunk is enqueuing (nullptr: single-style launches)
 };
 
 template <class T>
@@ -422,6 +441,7 @@ extern "C" int mst_engine_create(const mst_config* c, mst_engine** out) {
     if (const char* v = getenv("MST_PRECISE")) e->precise = atoi(v) != 0;
     if (const char* v = getenv("MST_LN128_M")) e->ln128_min_m = atoi(v);
     if (const char* v = getenv("MST_TRUNK")) e->trunk_groups = atoi(v) != 0;
+    if (const char* v = getenv("MST_STYLE_XCD")) e->style_xcd = atoi(v) != 0;
     CHECK(dmalloc(&e->trunk_cnt, (size_t)c->max_rows * 32));
     HIPCHECK(hipHostMalloc((void**)&e->trunk_err, 64, hipHostMallocDefault));
     e->trunk_err[0] = 0;
@@ -474,6 +494,14 @@ extern "C" void mst_engine_destroy(mst_engine* e) {
     (void)hipFree(e->ld_dev);
     (void)hipFree(e->rowflag);
     if (e->ld_pin) (void)hipHostFree(e->ld_pin);
+    for (LayerW& w : e->slot_w) {
+        void* q[] = {w.b_in, w.b_out, w.b1, w.b2, w.g1, w.be1, w.g2, w.be2, w.wtail, w.wqkv, w.wsm_in, w.wsm_out, w.wsm_1, w.wsm_2};
+        for (void* x : q) (void)hipFree(x);
+    }
+    (void)hipFree(e->style_tab);
+    (void)hipFree(e->style_stage);
+    (void)hipFree(e->plan_dev);
+    if (e->plan_ev) (void)hipEventDestroy(e->plan_ev);
     for (int i = 0; i < mst_engine::LD_SLOTS; i++) if (e->ld_ev[i]) (void)hipEventDestroy(e->ld_ev[i]);
     for (auto& pp : e->prof_pts) {
         (void)hipEventDestroy(pp.a);
@@ -1059,6 +1087,349 @@ extern "C" int mst_trunk_check(mst_engine* e) {          // after a synchronisat
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ several styles (csrc/mst_style.h)
+static StyleLayer style_record(const LayerW& w) {
+    return StyleLayer{w.wqkv, w.b_in, w.wtail, w.b_out, w.g1, w.be1, w.b1, w.b2, w.g2, w.be2, w.wsm_in, w.wsm_out, w.wsm_1, w.wsm_2};
+}
+static LayerW& slot_layer(mst_engine* e, int slot, int l) { return slot == 0 ? e->L[l] : e->slot_w[(size_t)(slot - 1) * 16 + l]; }
+
+// Tile heights the stack's launches use (16 NTB rows): the segment tables exist for each of them.
+static int style_h_index(int tile_rows) { return tile_rows / 16 - 1; }
+
+static int plan_segments(const int* slot_of_row, int nrows, int S, int tile_rows, StyleSeg* out, int cap) {
+    if (!slot_of_row || nrows < 1 || S < 1 || tile_rows < 1 || cap < 0) return -1;
+    const int M = nrows * S;
+    int n = 0;
+    for (int t0 = 0; t0 < M; t0 += tile_rows) {
+        const int t1 = t0 + tile_rows < M ? t0 + tile_rows : M;
+        int lo = t0;
+        while (lo < t1) {
+            const int slot = slot_of_row[lo / S];
+            int hi = (lo / S + 1) * S;                      // end of this clip
+            while (hi < t1 && slot_of_row[hi / S] == slot) hi += S;
+            if (hi > t1) hi = t1;
+            if (n >= cap) return -1;
+            out[n++] = StyleSeg{t0, lo, hi, slot};
+            lo = hi;
+        }
+    }
+    return n;
+}
+
+extern "C" int32_t mst_plan_style_segments(const int32_t* styles_host, int32_t nclips, int32_t S, int32_t tile_rows, int32_t* out, int32_t cap) {
+    if (!styles_host || !out) return (void)fail("mst_plan_style_segments: null argument"), -1;
+    if (nclips < 1 || S < 1 || tile_rows < 1 || cap < 0) return (void)fail("mst_plan_style_segments: bad sizes"), -1;
+    const int n = plan_segments(styles_host, nclips, S, tile_rows, reinterpret_cast<StyleSeg*>(out), cap);
+    if (n < 0) return (void)fail("mst_plan_style_segments: more than %d segments", cap), -1;
+    return n;
+}
+
+// XCD-affine order: items sorted (stably) by slot fill the block positions of XCD 0 (x, x + 8, ...), then XCD 1, ... (round-robin
+// dispatch: block b runs on XCD b % 8), so that one slot's workgroups share as few L2s as possible.  Returns order[position] = item.
+static std::vector<int> xcd_order(const std::vector<int>& slot_of_item) {
+    const int n = (int)slot_of_item.size();
+    std::vector<int> sorted(n), order(n);
+    for (int i = 0; i < n; i++) sorted[i] = i;
+    std::stable_sort(sorted.begin(), sorted.end(), [&](int a, int b) { return slot_of_item[a] < slot_of_item[b]; });
+    int k = 0;
+    for (int x = 0; x < 8; x++)
+        for (int p = x; p < n; p += 8) order[p] = sorted[k++];
+    return order;
+}
+
+extern "C" int mst_style_slots(mst_engine* e, int32_t n) {
+    if (!e) return fail("mst_style_slots: null engine");
+    if (n < 1 || n > 64) return fail("mst_style_slots: %d slots (1..64)", n);
+    if (n < e->nslots) return fail("mst_style_slots: the engine already has %d slots", e->nslots);
+    ON_DEVICE(e->cfg.device);
+    const int nl = e->cfg.num_layers;
+    e->slot_w.resize((size_t)(n - 1) * 16);
+    for (int s = e->nslots; s < n; s++) {
+        for (int l = 0; l < nl; l++) {
+            LayerW& w = slot_layer(e, s, l);
+            CHECK(dmalloc(&w.b_in, 3 * MST_D));
+            CHECK(dmalloc(&w.b_out, MST_D));
+            CHECK(dmalloc(&w.b1, MST_FF));
+            CHECK(dmalloc(&w.b2, MST_D));
+            CHECK(dmalloc(&w.g1, MST_D));
+            CHECK(dmalloc(&w.be1, MST_D));
+            CHECK(dmalloc(&w.g2, MST_D));
+            CHECK(dmalloc(&w.be2, MST_D));
+            CHECK(dmalloc(&w.wtail, TailCfg::LAYER_BYTES / 2));
+            CHECK(dmalloc(&w.wqkv, (size_t)3 * MST_D * MST_D));
+            CHECK(dmalloc(&w.wsm_in, (size_t)3 * MST_D * MST_D));
+            CHECK(dmalloc(&w.wsm_out, (size_t)MST_D * MST_D));
+            CHECK(dmalloc(&w.wsm_1, (size_t)MST_FF * MST_D));
+            CHECK(dmalloc(&w.wsm_2, (size_t)MST_D * MST_FF));
+        }
+    }
+    if (!e->style_stage) CHECK(dmalloc(&e->style_stage, (size_t)(3 * MST_D * MST_D + MST_D * MST_D + 2 * MST_FF * MST_D)));
+    std::vector<StyleLayer> tab((size_t)n * nl);
+    for (int s = 0; s < n; s++)
+        for (int l = 0; l < nl; l++) tab[(size_t)s * nl + l] = style_record(slot_layer(e, s, l));
+    (void)hipFree(e->style_tab);
+    e->style_tab = nullptr;
+    CHECK(dmalloc(&e->style_tab, tab.size()));
+    HIPCHECK(hipMemcpy(e->style_tab, tab.data(), tab.size() * sizeof(StyleLayer), hipMemcpyHostToDevice));
+    if (!e->plan_dev) {
+        // every slice layout of a call: row slots + clip order (2 ints per transformer row) and, per tile height h, at most
+        // (rows of the slice) / h + 1 tiles + (clips of the slice) segments of 4 ints; plus alignment slack per table
+        const size_t M = (size_t)e->cfg.max_rows * e->S_max, R = (size_t)e->cfg.max_rows, K = mst_engine::MAX_SLICES;
+        size_t cap = 2 * R + 8 * K;
+        for (int h = 16; h <= 64; h += 16) cap += 4 * (M / h + K + R) + 8 * K;
+        CHECK(dmalloc(&e->plan_dev, cap));
+        e->plan_cap = cap;
+    }
+    e->nslots = n;
+    return 0;
+}
+
+extern "C" int mst_load_layers_slot(mst_engine* e, int32_t slot, const float* const* srcs, void* stream) {
+    if (!e || !srcs) return fail("mst_load_layers_slot: null argument");
+    if (slot == 0) return mst_load_layers(e, srcs, stream);
+    if (slot < 0 || slot >= e->nslots) return fail("mst_load_layers_slot: slot %d outside 0..%d (mst_style_slots)", slot, e->nslots - 1);
+    hipStream_t st = (hipStream_t)stream;
+    ON_DEVICE(e->cfg.device);
+    const int nl = e->cfg.num_layers;
+    for (int i = 0; i < 12 * nl; i++) if (!srcs[i]) return fail("mst_load_layers_slot: null tensor %d", i);
+    f16* const w_in = e->style_stage;
+    f16* const w_out = w_in + 3 * MST_D * MST_D;
+    f16* const w1 = w_out + MST_D * MST_D;
+    f16* const w2 = w1 + MST_FF * MST_D;
+    for (int l = 0; l < nl; l++) {
+        LayerW& w = slot_layer(e, slot, l);
+        const float* const* s = srcs + 12 * l;
+        // the plain f16 matrices go to the staging buffer (stream-ordered: the previous layer's packs have read it), then the packings
+        CHECK(put_matrix(s[0], 3 * MST_D, MST_D, w_in, 3 * MST_D, MST_D, st));
+        CHECK(put_vector(s[1], 3 * MST_D, w.b_in, 3 * MST_D, st));
+        CHECK(put_matrix(s[2], MST_D, MST_D, w_out, MST_D, MST_D, st));
+        CHECK(put_vector(s[3], MST_D, w.b_out, MST_D, st));
+        CHECK(put_matrix(s[4], MST_FF, MST_D, w1, MST_FF, MST_D, st));
+        CHECK(put_vector(s[5], MST_FF, w.b1, MST_FF, st));
+        CHECK(put_matrix(s[6], MST_D, MST_FF, w2, MST_D, MST_FF, st));
+        CHECK(put_vector(s[7], MST_D, w.b2, MST_D, st));
+        CHECK(put_vector(s[8], MST_D, w.g1, MST_D, st));
+        CHECK(put_vector(s[9], MST_D, w.be1, MST_D, st));
+        CHECK(put_vector(s[10], MST_D, w.g2, MST_D, st));
+        CHECK(put_vector(s[11], MST_D, w.be2, MST_D, st));
+        hipLaunchKernelGGL(k_pack_qkv, dim3(384), dim3(256), 0, st, w_in, w.wqkv);
+        hipLaunchKernelGGL(k_pack_tail, dim3(640), dim3(256), 0, st, w_out, w1, w2, w.wtail);
+        hipLaunchKernelGGL(k_pack_blocks, dim3(192), dim3(256), 0, st, w_in, MST_D, 3 * MST_D, MST_D, w.wsm_in);
+        hipLaunchKernelGGL(k_pack_blocks, dim3(64), dim3(256), 0, st, w_out, MST_D, MST_D, MST_D, w.wsm_out);
+        hipLaunchKernelGGL(k_pack_blocks, dim3(128), dim3(256), 0, st, w1, MST_D, MST_FF, MST_D, w.wsm_1);
+        hipLaunchKernelGGL(k_pack_blocks, dim3(128), dim3(256), 0, st, w2, MST_FF, MST_D, MST_FF, w.wsm_2);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int mst_set_styles(mst_engine* e, const int32_t* styles_host, int32_t batch, void* stream) {
+    (void)stream;
+    if (!e) return fail("mst_set_styles: null engine");
+    if (!styles_host) { e->styles.clear(); return 0; }
+    if (batch < 1 || batch > e->cfg.max_rows) return fail("mst_set_styles: batch %d outside 1..%d", batch, e->cfg.max_rows);
+    for (int i = 0; i < batch; i++)
+        if (styles_host[i] < 0 || styles_host[i] >= e->nslots)
+            return fail("mst_set_styles: clip %d has style %d outside [0, %d)", i, styles_host[i], e->nslots);
+    e->styles.assign(styles_host, styles_host + batch);
+    return 0;
+}
+
+static bool styles_on(const mst_engine* e) { return e->nslots > 1 && !e->styles.empty(); }
+
+// The configurations the style-aware kernels cover; everything else is refused by name (never a silent single-style answer).
+static int style_check(const mst_engine* e, int batch, int frames) {
+    const char* what = nullptr;
+    if (e->precise) what = "precise mode (mst_set_precise / MST_PRECISE)";
+    else if (e->trunk_groups) what = "the resident trunk (mst_set_trunk_groups / MST_TRUNK)";
+    else if (!e->fuse_tail) what = "MST_FUSE_TAIL=0";
+    else if (e->fuse_qkv_attn != 1) what = "MST_FUSE_QKV_ATTN other than 1";
+    else if (!e->small_fast) what = "MST_SMALL_FAST=0";
+    else if (e->dbg_stage >= 0) what = "a debug stop (mst_debug_stop_after)";
+    else if (e->graph_on) what = "graph replay (MST_GRAPH)";
+    else if (e->prof_on) what = "profiling (mst_profile_enable)";
+    else if (frames <= 16) what = "clips of 16 frames or fewer (split-operand kernels)";
+    else if (!qkv_attn2_fits(frames + 1)) what = "clips of more than 207 frames";
+    if (what) return fail("several styles: %s is not supported with more than one style slot", what);
+    if ((int)e->styles.size() != batch) return fail("several styles: mst_set_styles named %zu clips, the call has %d", e->styles.size(), batch);
+    return 0;
+}
+
+// This call's tables: for each slice (enqueue_step's split of the batch; cond + uncond twins of a clip share its slot) the slot of every
+// transformer row, the clip order of the attention launch and the segments of every tile height -- built once and uploaded in ONE copy.
+static int style_plan(mst_engine* e, int batch, int cfg, int frames, int nsl, hipStream_t st) {
+    const int S = frames + 1;
+    if (!e->plan_ev) HIPCHECK(hipEventCreateWithFlags(&e->plan_ev, hipEventDisableTiming));
+    HIPCHECK(hipEventSynchronize(e->plan_ev));
+    std::vector<int>& h = e->plan_host;
+    h.clear();
+    auto align4 = [&]() { while (h.size() & 3) h.push_back(0); };
+    const int per = (batch + nsl - 1) / nsl;
+    for (int sl = 0; sl < nsl; sl++) {
+        StyleSlice& ps = e->plan_sl[sl];
+        ps = StyleSlice{};
+        const int c0 = sl * per, nb = (c0 + per <= batch) ? per : batch - c0;
+        if (nb <= 0) continue;
+        const int rows = cfg ? 2 * nb : nb;
+        std::vector<int> slot(rows);
+        for (int r = 0; r < rows; r++) slot[r] = e->styles[c0 + r % nb];
+        ps.rows = rows;
+        align4();
+        ps.off_slot = (int)h.size();
+        h.insert(h.end(), slot.begin(), slot.end());
+        ps.off_order = (int)h.size();
+        if (e->style_xcd) { const std::vector<int> o = xcd_order(slot); h.insert(h.end(), o.begin(), o.end()); }
+        else for (int r = 0; r < rows; r++) h.push_back(r);
+        for (int hi = 0; hi < 4; hi++) {
+            const int tr = 16 * (hi + 1), cap = (rows * S) / tr + 1 + rows;
+            std::vector<StyleSeg> seg(cap);
+            const int n = plan_segments(slot.data(), rows, S, tr, seg.data(), cap);
+            if (n < 0) return fail("several styles: segment table overflow");
+            seg.resize(n);
+            if (e->style_xcd) {
+                std::vector<int> key(n);
+                for (int i = 0; i < n; i++) key[i] = seg[i].slot;
+                const std::vector<int> o = xcd_order(key);
+                std::vector<StyleSeg> re(n);
+                for (int i = 0; i < n; i++) re[i] = seg[o[i]];
+                seg.swap(re);
+            }
+            align4();
+            ps.off_seg[hi] = (int)h.size();
+            ps.nseg[hi] = n;
+            for (const StyleSeg& g : seg) { h.push_back(g.row0); h.push_back(g.row_lo); h.push_back(g.row_hi); h.push_back(g.slot); }
+        }
+    }
+    if (h.size() > e->plan_cap) return fail("several styles: plan of %zu ints exceeds %zu", h.size(), e->plan_cap);
+    HIPCHECK(hipMemcpyAsync(e->plan_dev, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipEventRecord(e->plan_ev, st));
+    return 0;
+}
+
+template <int KS, int MODE, int LNF, int NTB>
+static int launch_rows_seg(mst_engine* e, const StyleSlice& ps, int l, const f16* X, void* out, int ldo, int N, const LnRows& ln, hipStream_t st) {
+    constexpr int smem = 64 * (KS / 16) * 1024 / (4 / NTB);
+    if constexpr (NTB == 4) CHECK(ensure_dyn_lds((const void*)k_rows_gemm_seg<KS, MODE, LNF, NTB>, smem));
+    const int hi = style_h_index(16 * NTB), nl = e->cfg.num_layers;
+    const StyleSeg* segs = reinterpret_cast<const StyleSeg*>(e->plan_dev + ps.off_seg[hi]);
+    hipLaunchKernelGGL((k_rows_gemm_seg<KS, MODE, LNF, NTB>), dim3(ps.nseg[hi], N / 128), dim3(512), smem, st, X, e->style_tab + l,
+                       e->style_tab + (l > 0 ? l - 1 : 0), nl, segs, out, ldo, ln);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+// launch_rows_gemm's tile-height rule, per segment table
+template <int KS, int MODE>
+static int launch_rows_seg_m(mst_engine* e, const StyleSlice& ps, int l, int M, const f16* X, void* out, int ldo, int N, hipStream_t st) {
+    if (M <= g_rows_ntb1_m) return launch_rows_seg<KS, MODE, 0, 1>(e, ps, l, X, out, ldo, N, LnRows{}, st);
+    if (M > g_rows_ntb2_from) return launch_rows_seg<KS, MODE, 0, 2>(e, ps, l, X, out, ldo, N, LnRows{}, st);
+    return launch_rows_seg<KS, MODE, 0, 4>(e, ps, l, X, out, ldo, N, LnRows{}, st);
+}
+static int launch_ln_style(mst_engine* e, const StyleSlice& ps, int l, int which, const float* acc, f16* hi, f16* lo, int M, int S, hipStream_t st,
+                           f16* ohi = nullptr, f16* olo = nullptr) {
+    hipLaunchKernelGGL(k_ln_rows_style, dim3((M + 3) / 4), dim3(256), 0, st, acc, e->style_tab + l, e->cfg.num_layers, which, e->plan_dev + ps.off_slot,
+                       S, hi, lo, M, ohi, olo);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+template <int NT16>
+static int launch_qkv_attn2_style_n(mst_engine* e, const StyleSlice& ps, int l, const WS& ws, int S, int rows, hipStream_t st) {
+    auto kern = k_qkv_attention2_style<NT16>;
+    constexpr int smem = QA2Tile<NT16>::SMEM;
+    CHECK(ensure_dyn_lds((const void*)kern, smem));
+    hipLaunchKernelGGL(kern, dim3(rows * MST_H), dim3(512), smem, st, ws.hx, e->style_tab + l, e->cfg.num_layers, e->plan_dev + ps.off_slot,
+                       e->plan_dev + ps.off_order, ws.att, S);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+static int launch_qkv_attn2_style(mst_engine* e, const StyleSlice& ps, int l, const WS& ws, int S, int rows, hipStream_t st) {
+    const int n16 = (S + 15) / 16;
+    switch (n16 == 13 ? 13 : (n16 + 1) / 2 * 2) {
+        case 2: return launch_qkv_attn2_style_n<2>(e, ps, l, ws, S, rows, st);
+        case 4: return launch_qkv_attn2_style_n<4>(e, ps, l, ws, S, rows, st);
+        case 6: return launch_qkv_attn2_style_n<6>(e, ps, l, ws, S, rows, st);
+        case 8: return launch_qkv_attn2_style_n<8>(e, ps, l, ws, S, rows, st);
+        case 10: return launch_qkv_attn2_style_n<10>(e, ps, l, ws, S, rows, st);
+        case 12: return launch_qkv_attn2_style_n<12>(e, ps, l, ws, S, rows, st);
+        case 13: return launch_qkv_attn2_style_n<13>(e, ps, l, ws, S, rows, st);
+    }
+    return fail("attention: S=%d unsupported", S);
+}
+static int launch_tail_style(mst_engine* e, const StyleSlice& ps, int l, const WS& ws, int M, hipStream_t st) {
+    int ntb = e->tail_ntb;                                   // launch_tail's tile-height rule
+    if (ntb == 0) {
+        ntb = 4;
+        if (e->cur_slices == 1) {
+            if ((M + 31) / 32 <= 256) ntb = 2;
+            else if ((M + 47) / 48 <= 256) ntb = 3;
+        }
+    }
+    const int hi = style_h_index(16 * ntb), nl = e->cfg.num_layers;
+    const StyleSeg* segs = reinterpret_cast<const StyleSeg*>(e->plan_dev + ps.off_seg[hi]);
+#define TAIL_SEG(N_)                                                                                                               \
+    do {                                                                                                                           \
+        CHECK(ensure_dyn_lds((const void*)k_layer_tail_seg<N_>, TailCfg::SMEM));                                                   \
+        hipLaunchKernelGGL(k_layer_tail_seg<N_>, dim3(ps.nseg[hi]), dim3(512), TailCfg::SMEM, st, ws.att, e->style_tab + l, nl, segs, \
+                           ws.hx, ws.hl, e->gelu_tab);                                                                             \
+    } while (0)
+    if (ntb == 2) TAIL_SEG(2);
+    else if (ntb == 3) TAIL_SEG(3);
+    else TAIL_SEG(4);
+#undef TAIL_SEG
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// run_trunk for a batch of several styles: the default fused path (style_check has refused everything else), each launch reading the
+// slice's tables.  Same launch sequence and tile heights as the single-style path.
+static int run_trunk_style(mst_engine* e, const WS& ws, int rows, int T, hipStream_t st, const StyleSlice& ps) {
+    const int S = T + 1, M = rows * S, NL = e->cfg.num_layers;
+    if (ps.rows != rows) return fail("several styles: slice of %d rows, plan of %d", rows, ps.rows);
+    const bool small = e->small_m > 0 && M <= e->small_m;
+    const bool lnf = small && e->small_ln && M <= e->small_ln_m;
+    for (int l = 0; small && l < NL; l++) {
+        {
+            ProfScope pq(e, FAM_QKV, st);
+            if (lnf && l > 0) {
+                const LnRows ln{ws.zacc, nullptr, nullptr, nullptr, ws.hx2, ws.hl2, ws.hx, ws.hl};
+                CHECK((launch_rows_seg<16, 0, 1, 1>(e, ps, l, nullptr, ws.qkv, 3 * MST_D, 3 * MST_D, ln, st)));
+            } else CHECK((launch_rows_seg_m<16, 0>(e, ps, l, M, ws.hx, ws.qkv, 3 * MST_D, 3 * MST_D, st)));
+        }
+        {
+            ProfScope pa(e, FAM_ATTN, st);
+            CHECK(launch_attn(ws.qkv, ws.att, S, rows, st, 1, nullptr));
+        }
+        {
+            ProfScope po(e, FAM_OUTPROJ_LN, st);
+            CHECK((launch_rows_seg_m<16, 2>(e, ps, l, M, ws.att, ws.zacc, MST_D, MST_D, st)));
+            if (!lnf) CHECK(launch_ln_style(e, ps, l, 0, ws.zacc, ws.hx, ws.hl, M, S, st));
+        }
+        {
+            ProfScope p1(e, FAM_FFN1, st);
+            if (lnf) {
+                const LnRows ln{ws.zacc, nullptr, nullptr, nullptr, ws.hx, ws.hl, ws.hx2, ws.hl2};
+                CHECK((launch_rows_seg<16, 1, 1, 1>(e, ps, l, nullptr, ws.hid, MST_FF, MST_FF, ln, st)));
+            } else CHECK((launch_rows_seg_m<16, 1>(e, ps, l, M, ws.hx, ws.hid, MST_FF, MST_FF, st)));
+        }
+        {
+            ProfScope p2(e, FAM_FFN2_LN, st);
+            CHECK((launch_rows_seg_m<32, 2>(e, ps, l, M, ws.hid, ws.zacc, MST_D, MST_D, st)));
+            if (!lnf) CHECK(launch_ln_style(e, ps, l, 1, ws.zacc, ws.hx, ws.hl, M, S, st));
+            else if (l == NL - 1) CHECK(launch_ln_style(e, ps, l, 1, ws.zacc, ws.hx2, ws.hl2, M, S, st, ws.hx, ws.hl));
+        }
+    }
+    for (int l = 0; !small && l < NL; l++) {
+        {
+            ProfScope pq(e, FAM_QKV_ATTN, st);
+            CHECK(launch_qkv_attn2_style(e, ps, l, ws, S, rows, st));
+        }
+        {
+            ProfScope pt(e, FAM_TAIL, st);
+            CHECK(launch_tail_style(e, ps, l, ws, M, st));
+        }
+    }
+    return 0;
+}
+
 // K3 .. K8: token stream through the encoder stack.  rows = clips through the transformer.
 // K1-K3: conditioning token + pose embedding of the frames -> token stream rows (ws.hx / ws.hl)
 struct LoopRef { const LoopDev* ld = nullptr; int joff = 0; unsigned long long eo = 0; bool frames_ready = false; bool stream_ready = false; };   // stream_ready: the previous step's k_embed_out already embedded this step (token stream and conditioning tokens are in ws.hx / ws.hl)   // frames_ready: the previous step's epilogue already wrote ws.xt   // loop mode of a step's kernels (see LoopDev)
@@ -1124,6 +1495,7 @@ static int run_trunk(mst_engine* e, const WS& ws, const float* x, int clips_x, i
     const int S = T + 1, M = rows * S;
     CHECK(assemble_stream(e, ws, x, clips_x, rows, T, temb_uniform_row, temb_mod, st, tp_uncond, lr));
     if (e->dbg_stage == 0) return 0;
+    if (e->style_cur) return run_trunk_style(e, ws, rows, T, st, *e->style_cur);
 #define DBG_STOP(stage) if (e->dbg_layer == l && e->dbg_stage == stage) return 0;
     const bool small = e->precise || (e->small_m > 0 && M <= e->small_m);
     // Clips of at most 16 frames: so few values are averaged per output that the f16 rounding of the ACTIVATION operands shows at the
@@ -1374,7 +1746,15 @@ extern "C" int mst_forward(mst_engine* e, const float* x, const int64_t* t, cons
     CHECK(timestep_rows(e, (const long long*)t, batch, st));
     const int rows = cfg ? 2 * batch : batch;
     const WS ws = ws_slice(e, 0, frames);
-    CHECK(run_trunk(e, ws, x, batch, rows, frames, -1, batch, st, batch));
+    e->style_cur = nullptr;
+    if (styles_on(e)) {
+        CHECK(style_check(e, batch, frames));
+        CHECK(style_plan(e, batch, cfg, frames, 1, st));
+        e->style_cur = &e->plan_sl[0];
+    }
+    const int rc = run_trunk(e, ws, x, batch, rows, frames, -1, batch, st, batch);
+    e->style_cur = nullptr;
+    CHECK(rc);
     StepArgs sa{};
     sa.scale = scale;
     return trunk_settle(e, st, launch_out_nt<0>(e, ws, cfg, batch, frames, out, sa, st, nullptr, nullptr, 1, false, true));
@@ -1432,7 +1812,10 @@ static int enqueue_step(mst_engine* e, const LoopPlan& p, int joff, int nsj, boo
         ws.textproj = e->textproj + (size_t)c0 * MST_D;
         hipStream_t ss = p.streams[sl];
         LoopRef lr{e->ld_dev, joff, eo, frames_ready, stream_ready};
-        CHECK(run_trunk(e, ws, nullptr, nb, a->cfg ? 2 * nb : nb, a->frames, 0, 0, ss, a->batch, lr));
+        e->style_cur = styles_on(e) ? &e->plan_sl[sl] : nullptr;     // (mst_sample_loop planned nsj = p.nsl slices: instrumented steps are refused)
+        const int rc = run_trunk(e, ws, nullptr, nb, a->cfg ? 2 * nb : nb, a->frames, 0, 0, ss, a->batch, lr);
+        e->style_cur = nullptr;
+        CHECK(rc);
         const DEpiEmbedIn next_epi = embed_in_epi(e, ws, nb, nb, a->frames, 0, 0, a->batch, e->ld_dev, joff + 1);
         const DEpiEmbedIn* next = embed_next ? &next_epi : nullptr;
         StepArgs sa{};
@@ -1484,6 +1867,7 @@ extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_l
     if (!a->x_dev || (a->cfg && !a->scale_dev)) return fail("mst_sample_loop: null x / scale");
     if (a->noise_mode == MST_NOISE_BUFFER && !a->noise_dev) return fail("mst_sample_loop: noise buffer missing");
     if (a->sampler != MST_SAMPLER_DDPM && a->sampler != MST_SAMPLER_DDIM) return fail("mst_sample_loop: bad sampler");
+    if (styles_on(e)) CHECK(style_check(e, a->batch, a->frames));
     hipStream_t caller = (hipStream_t)stream;
     ON_DEVICE(e->cfg.device);
     // The loop runs on engine-owned streams: behind everything the caller has enqueued (ev_in), and the caller's stream
@@ -1502,6 +1886,7 @@ extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_l
     // flat in the block count at this size).  CFG batches are sliced the same way (cond + uncond twins stay together).
     LoopPlan p{s, a, loop_slices_for(e, a->batch, a->cfg, a->frames), (size_t)e->cfg.feats * a->frames, (size_t)a->batch * e->cfg.feats * a->frames,
                {st, e->aux_stream[0], e->aux_stream[1], e->aux_stream[2], e->aux_stream[3], e->aux_stream[4], e->aux_stream[5], e->aux_stream[6]}};
+    if (styles_on(e)) CHECK(style_plan(e, a->batch, a->cfg, a->frames, p.nsl, st));     // before the fork: every slice stream is behind it
     // per-call arguments -> device (pinned staging slot; the slot's previous upload has long completed when it comes round again)
     {
         const int slot = e->ld_next;

@@ -65,17 +65,19 @@ struct FfnTrain { f16* pre; Drop d; };
 // NTB: the tile is 16 NTB tokens high.  64 where the rows are read; 16 where they are made -- a workgroup's LayerNorm of 64 rows is
 // ~830 VALU instructions per lane on two waves per SIMD (2.9 us measured on top of the 2.9 us GEMM, more than the launch it replaces),
 // of 16 rows a quarter of that, and at the row counts this path serves (a clip or two) the extra workgroups find idle CUs.
-template <int KS, int MODE, int LNF = 0, int NTB = 4>
-__global__ __launch_bounds__(512) void k_rows_gemm(const f16* __restrict__ X, const f16* __restrict__ wpk, const float* __restrict__ bias,
-                                                   void* __restrict__ out, int ldo, int M, LnRows ln = {}, FfnTrain ft = {}) {
+// SEG (k_rows_gemm_seg, mst_style.h): the tile starting at seg_row0 is computed whole, only its rows [row_lo, M) are stored (M: the segment's end).
+template <int KS, int MODE, int LNF, int NTB, bool SEG>
+__device__ __forceinline__ void rows_gemm_body(const f16* __restrict__ X, const f16* __restrict__ wpk, const float* __restrict__ bias,
+                                               void* __restrict__ out, int ldo, int M, const LnRows& ln, const FfnTrain& ft, int seg_row0, int row_lo) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(!SEG || MODE != 3, "segments are a sampling-launch layout");
     static_assert(KS == 16 || KS == 32, "K = 512 or 1024");
     static_assert(!LNF || KS == 16, "a LayerNorm row is 512 wide");
     constexpr int NP = KS / 16, ROWB = NP * 1024, D = 8, RPW = 2 * NTB, LB = RPW < 4 ? RPW : 4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int t16 = lane & 15, q4 = lane >> 4;
-    const int tok0 = blockIdx.x * (16 * NTB);
+    const int tok0 = SEG ? seg_row0 : blockIdx.x * (16 * NTB);
     const unsigned smem_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
     // rows [RPW w, RPW w + RPW) of the tile: NP pieces each
 #pragma unroll
@@ -161,7 +163,7 @@ __global__ __launch_bounds__(512) void k_rows_gemm(const f16* __restrict__ X, co
                             char* dst = smem + r * ROWB + (lane & 1) * 8;
                             *reinterpret_cast<uint2*>(dst + (((lane >> 1) ^ (r & 15)) << 4)) = ha;
                             *reinterpret_cast<uint2*>(dst + (((32 + (lane >> 1)) ^ (r & 15)) << 4)) = hb;
-                            if (blockIdx.y == 0 && tok < M) {
+                            if (blockIdx.y == 0 && tok < M && (!SEG || tok >= row_lo)) {
                                 const size_t off = (size_t)tok * MST_D;
                                 *reinterpret_cast<uint2*>(ln.out_hi + off + fa) = ha;
                                 *reinterpret_cast<uint2*>(ln.out_lo + off + fa) = la;
@@ -189,7 +191,7 @@ __global__ __launch_bounds__(512) void k_rows_gemm(const f16* __restrict__ X, co
 #pragma unroll
     for (int tb = 0; tb < NTB; tb++) {
         const int tok = tok0 + 16 * tb + t16;
-        if (tok >= M) continue;
+        if (tok >= M || (SEG && tok < row_lo)) continue;
         f32x4 v = acc[tb] + bv;
         if constexpr (MODE == 3) {
             const size_t o = (size_t)tok * ldo + f;
@@ -206,6 +208,11 @@ __global__ __launch_bounds__(512) void k_rows_gemm(const f16* __restrict__ X, co
         if (MODE == 2) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + (size_t)tok * ldo + f) = v;
         else *reinterpret_cast<uint2*>(reinterpret_cast<f16*>(out) + (size_t)tok * ldo + f) = pack4_f16(v[0], v[1], v[2], v[3]);
     }
+}
+template <int KS, int MODE, int LNF = 0, int NTB = 4>
+__global__ __launch_bounds__(512) void k_rows_gemm(const f16* __restrict__ X, const f16* __restrict__ wpk, const float* __restrict__ bias,
+                                                   void* __restrict__ out, int ldo, int M, LnRows ln = {}, FfnTrain ft = {}) {
+    rows_gemm_body<KS, MODE, LNF, NTB, false>(X, wpk, bias, out, ldo, M, ln, ft, 0, 0);
 }
 
 }  // namespace mst

@@ -188,15 +188,18 @@ __device__ __forceinline__ void tail_glds1(unsigned voff, unsigned long long sba
 // workgroup; the resident-group trunk (mst_trunk.h) calls it once per layer with PERSIST = true: the tables, the FFN1 bias and the first D
 // weight fragments are requested, THEN the workgroup waits for its clip's four attention heads (group_wait) and only then requests its
 // att rows; LayerNorm2's rows leave as write-through stores.
-template <int NTB, bool PERSIST, bool TRAIN = false>
+// SEG (k_layer_tail_seg, mst_style.h): the tile is computed whole, but only its rows [row_lo, M) are stored -- one segment of a tile
+// whose rows belong to several style slots; M is then the segment's end row (rows at and beyond it are clamped on load as usual).
+template <int NTB, bool PERSIST, bool TRAIN = false, bool SEG = false>
 __device__ __forceinline__ void tail_body(char* smem, const f16* __restrict__ att, const f16* __restrict__ wt,
                                           const float* __restrict__ b_out, const float* __restrict__ g1, const float* __restrict__ be1,
                                           const float* __restrict__ b1, const float* __restrict__ b2,
                                           const float* __restrict__ g2, const float* __restrict__ be2,
                                           f16* __restrict__ hx, f16* __restrict__ hl, const float* __restrict__ gelu_tab, int M, int tok0,
-                                          const GroupSync sync, int wave_in, const TailTrain& tt = TailTrain{}) {
+                                          const GroupSync sync, int wave_in, const TailTrain& tt = TailTrain{}, int row_lo = 0) {
     using C = TailCfg;
     static_assert(!(TRAIN && PERSIST), "the training forward is one launch per layer");
+    static_assert(!(SEG && (TRAIN || PERSIST)), "segments are a sampling-launch layout");
     const f16* const rin_h = TRAIN ? tt.xin_h : hx;                // LayerNorm1's residual rows (TRAIN: hx / hl are the OUTPUT stream)
     const f16* const rin_l = TRAIN ? tt.xin_l : hl;
     // Fragments in flight per wave.  TRAIN: 8 -- the inference kernel measures the same at 8 and 16, and the 32 registers pay for the
@@ -793,7 +796,7 @@ __device__ __forceinline__ void tail_body(char* smem, const f16* __restrict__ at
 #pragma unroll
         for (int r = 0; r < RPW; r++) {
             const int tok = tok0 + RPW * wave + r;
-            if (tok < M) {
+            if (tok < M && (!SEG || tok >= row_lo)) {
                 const size_t off = (size_t)tok * MST_D;
                 uint2 ha, la, hb, lb;
                 split4_f16(__builtin_elementwise_fma(xa[r], ga * rstd[r], ea), ha, la);

@@ -97,6 +97,13 @@ def _unwrap(model):
     return (model if hasattr(model, "mst_engine") else None), cfg, tmap
 
 
+def _refuse_bank(model, what):
+    """A StyleBank samples only: fine-tuning (every autograd-carrying sampler) stays per style."""
+    d, _, _ = _unwrap(model)
+    if getattr(d, "is_style_bank", False):
+        raise RuntimeError(f"{what}: a StyleBank does not run under autograd; fine-tune each StyleDiffusion on its own")
+
+
 class GaussianDiffusion:
     TABLES = ("betas", "alphas_cumprod", "alphas_cumprod_prev", "alphas_cumprod_next", "sqrt_alphas_cumprod",
               "sqrt_one_minus_alphas_cumprod", "log_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod",
@@ -310,6 +317,7 @@ class GaussianDiffusion:
         reference the step input is cut from the previous step's graph (`x.detach()`); gradients reach the parameters through
         every step's x0-hat."""
         from .fused_ops import FusedStepFn
+        _refuse_bank(model, "p_sample_with_grad / ddim_sample_with_grad")
         if self.model_mean_type != ModelMeanType.START_X:
             raise NotImplementedError("this model family predicts x_start (utils/model_util.py:172)")
         assert t.shape == (x.shape[0],)
@@ -407,6 +415,7 @@ class GaussianDiffusion:
             raise NotImplementedError("randomize_class is an image-diffusion leftover, unused by this model family")
         with_grad = cond_fn_with_grad or pred_xstart_in_graph
         if with_grad:
+            _refuse_bank(model, "cond_fn_with_grad / pred_xstart_in_graph sampling")
             # the steps' inputs are cut from each other's graphs (x.detach() in *_with_grad): native model calls on a single clip share
             # one activation tape and ONE backward pass, and may run on a side stream (model/native_stack.ChainedCalls) -- the loop's
             # set-up (x_T, q_sample of the init image) included, so that it is ordered with them; anything else is untouched.  The

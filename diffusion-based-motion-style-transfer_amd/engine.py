@@ -102,6 +102,18 @@ class Schedule:
         return sample, xstart
 
 
+def plan_style_segments(styles, S, tile_rows):
+    """Host-only (no GPU): the {row0, row_lo, row_hi, slot} segments the style-aware kernels run for rows of clips with these slots."""
+    s = np.ascontiguousarray(np.asarray(styles, dtype=np.int32).reshape(-1))
+    cap = (s.size * S) // tile_rows + 1 + s.size
+    out = np.zeros((cap, 4), dtype=np.int32)
+    n = N.lib().mst_plan_style_segments(s.ctypes.data_as(C.c_void_p), int(s.size), int(S), int(tile_rows),
+                                        out.ctypes.data_as(C.c_void_p), int(cap))
+    if n < 0:
+        raise RuntimeError(N.lib().mst_last_error().decode())
+    return out[:n].copy()
+
+
 class DenoiserEngine:
     def __init__(self, feats, max_frames, max_rows, num_layers=8, device="cuda:0", latent_dim=512, num_heads=4,
                  ff_size=1024, clip_dim=512, pe_len=5000):
@@ -223,6 +235,32 @@ class DenoiserEngine:
                 "gain_outlier": worst_gain >= self.GAIN_OUTLIER, "weight_scale_above_threshold": worst_w >= self.WEIGHT_SCALE,
                 "recommend_precise": bool(why), "why": "; ".join(why)}
 
+    # ------------------------------------------------------------------------------ several styles (csrc/mst_style.h)
+    def style_slots(self, n):
+        """Hold n style slots: slot 0 is this engine's own weights, slots 1 .. n-1 only what sampling reads."""
+        N.check(N.lib().mst_style_slots(self.handle, int(n)))
+        self.num_slots = int(n)
+
+    def load_layers_slot(self, slot, tensors):
+        """The stack's tensors (num_layers x LAYER_TENSORS order; float32, contiguous, on this device) into one slot."""
+        if slot == 0:
+            return self.load_layers(tensors)
+        assert len(tensors) == 12 * self.num_layers
+        for t in tensors:
+            if not (t.is_cuda and t.device == self.device and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("load_layers_slot wants float32 contiguous tensors on the engine's device")
+        arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        N.check(N.lib().mst_load_layers_slot(self.handle, int(slot), arr, N.stream_ptr(self.device)))
+
+    def set_styles(self, styles):
+        """Slot of every clip of the following forward / sample_loop calls (a sequence or tensor of ints), or None."""
+        if styles is None:
+            N.check(N.lib().mst_set_styles(self.handle, None, 0, N.stream_ptr(self.device)))
+            return
+        s = np.ascontiguousarray(np.asarray(styles.detach().cpu() if isinstance(styles, torch.Tensor) else styles,
+                                            dtype=np.int64).reshape(-1).astype(np.int32))
+        N.check(N.lib().mst_set_styles(self.handle, s.ctypes.data_as(C.c_void_p), int(s.size), N.stream_ptr(self.device)))
+
     # ------------------------------------------------------------------------------ conditioning
     def set_text(self, text_emb, keep=None, cfg=False, drop=None):
         """drop: the Bernoulli mask of the training-mode mask_cond as drawn (1 = dropped): cond * (1 - drop) inside the projection launch."""
@@ -234,11 +272,13 @@ class DenoiserEngine:
                 raise ValueError(f"set_text: a drop mask of {dr.numel()} entries for {te.shape[0]} text embeddings")
             N.check(N.lib().mst_set_text_dropped(self.handle, N.ptr(te), N.ptr(dr), te.shape[0], N.stream_ptr(self.device)))
             self._text_keepalive = (te, dr)
+            self.text_rows = te.shape[0]
             return
         kp = None if keep is None else _f32c(keep, self.device, "keep")
         N.check(N.lib().mst_set_text(self.handle, N.ptr(te), N.ptr(kp), te.shape[0], int(bool(cfg)),
                                      N.stream_ptr(self.device)))
         self._text_keepalive = (te, kp)
+        self.text_rows = te.shape[0]
 
     # ------------------------------------------------------------------------------ model call
     def forward(self, x, t, scale=None, cfg=False):

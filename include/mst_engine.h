@@ -365,6 +365,25 @@ int mst_set_precise(mst_engine* e, int32_t on);
  * bit-identical either way.  Also MST_TRUNK=1 / 0.  mst_trunk_check: after the caller has synchronised, 0 when every hand-off of every
  * such launch arrived (a bounded wait that gives up sets a host-visible word instead of hanging the device). */
 int mst_set_trunk_groups(mst_engine* e, int32_t on);
+
+/* Several fine-tuned styles in one batch (csrc/mst_style.h).  Replaces: one StyleDiffusion per style, each sampled by its own loop
+ * (sample/demo_style_transfer.py:74-85, 244-258); two styles differ only in model/mdm_forstyledataset.py:602-625's seqTransEncoder.
+ * mst_style_slots: the engine holds n slots (n >= the current count).  Slot 0 is the engine's own weights (mst_load_weight /
+ * mst_load_layers, training untouched); slots 1 .. n-1 hold only what sampling reads -- biases and LayerNorm vectors and the packed
+ * matrices of the fused QKV + attention, fused tail and small-launch kernels (about 64 MB each at 8 layers). */
+int mst_style_slots(mst_engine* e, int32_t n);
+/* The 12 x num_layers stack tensors of one slot, in mst_load_layers' order (float32 device pointers), packed on `stream` as slot 0's
+ * copies are packed (mst_load_layers for slot 0).  Not in precise mode (the extra slots have no lo halves). */
+int mst_load_layers_slot(mst_engine* e, int32_t slot, const float* const* srcs_host_array, void* stream);
+/* The slot of every clip of the next mst_forward / mst_sample_loop calls (host int32[batch], any order; under CFG a clip's
+ * unconditional twin uses the clip's slot).  styles_host = NULL: back to the single-style behaviour.  With more than one slot the
+ * calls refuse (and name) every configuration the style-aware kernels do not cover: precise mode, the resident trunk, MST_FUSE_TAIL=0,
+ * MST_FUSE_QKV_ATTN other than 1, MST_SMALL_FAST=0, clips of <= 16 or > 207 frames, debug stops, graph replay, profiling. */
+int mst_set_styles(mst_engine* e, const int32_t* styles_host, int32_t batch, void* stream);
+/* Host-only planner (no GPU): split every tile of `tile_rows` token rows of nclips x S rows into maximal runs of one slot.  Writes
+ * {row0, row_lo, row_hi, slot} int32 records to out (at most cap of them); returns their count, or -1 (mst_last_error) if cap is
+ * too small.  At most tiles + nclips records. */
+int32_t mst_plan_style_segments(const int32_t* styles_host, int32_t nclips, int32_t S, int32_t tile_rows, int32_t* out, int32_t cap);
 int mst_trunk_check(mst_engine* e);
 
 /* Debug / test hooks (no reference counterpart): stop the encoder stack after (layer, stage) --
