@@ -390,6 +390,8 @@ class GaussianDiffusion:
         else:
             chunk = max(1, min(int(self.noise_chunk), int(self.noise_chunk_bytes // (x.numel() * 4))))
         seed = int(th.randint(0, 2 ** 31 - 1, (1,)).item()) if self.noise_source == "philox" else 0
+        if cfg is not None:
+            eng.check_guidance_scale(scale)                 # once per loop (engine.CFG_SCALE_MAX), not per chunk or step
         it = range(0, len(indices), chunk)
         if progress:
             from tqdm.auto import tqdm

@@ -13,6 +13,12 @@ from . import _native as N
 SAMPLER_DDPM, SAMPLER_DDIM = 0, 1
 NOISE_BUFFER, NOISE_PHILOX = 0, 1
 
+# Largest classifier-free guidance factor (the larger of s and 1 - s per clip) at which the default f16-operand path was measured to
+# stay within 1e-3 relative L2 of the fp32 reference with 10 % to spare: worst clip 8.3e-4 at 3.0, 1.10e-3 at 4.0 over both shapes and
+# both tile paths (tests/test_gpu_cfg_precision.py, profiles/r07_cfg_sweep.txt).  The blend u + s (c - u)
+# amplifies the operand rounding of c and u by about s: above this, a guided call warns once per engine and names precise mode.
+CFG_SCALE_MAX = 3.0
+
 # order of enum mst_table; names are the reference's attribute names (gaussian_diffusion.py:183-219)
 TABLE_ORDER = ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod", "posterior_mean_coef1",
                "posterior_mean_coef2", "_log_variance", "sqrt_recip_alphas_cumprod",
@@ -409,6 +415,8 @@ class DenoiserEngine:
         noise: [nsteps,B,F,1,T] tensor (injected draws) or None -> in-kernel Philox with `seed`.
         Returns x (and the [nsteps,B,F,1,T] x0-hat dump when requested)."""
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        if cfg:
+            self.check_guidance_scale(scale)
         B, F, one, T = x.shape
         nsteps = t_start - t_end + 1
         a = N.MstLoopArgs()
@@ -475,6 +483,29 @@ class DenoiserEngine:
             torch.cuda.current_stream(self.device).synchronize()
             rc = 0
         N.check(rc)
+
+    def check_guidance_scale(self, scale):
+        """Warn (once per engine, through `warnings.warn`) when a guided call's scale puts the default path above the 1e-3 bar,
+        i.e. above CFG_SCALE_MAX.  A device tensor costs one host synchronisation the first time that tensor object (at that
+        version) is seen, none after: loops call this once, not per step."""
+        if scale is None or self._precise_on or getattr(self, "_cfg_warned", False):
+            return
+        if isinstance(scale, torch.Tensor):
+            seen = getattr(self, "_cfg_seen", None)
+            if seen is not None and seen[0] is scale and seen[1] == scale._version:
+                return
+            self._cfg_seen = (scale, scale._version)
+            s = scale.detach().float()
+            g = float(torch.maximum(s, 1.0 - s).max()) if s.numel() else 0.0
+        else:
+            s = np.asarray(scale, dtype=np.float64)
+            g = float(np.maximum(s, 1.0 - s).max()) if s.size else 0.0
+        if g > CFG_SCALE_MAX:
+            self._cfg_warned = True
+            import warnings
+            warnings.warn(f"mst_amd: classifier-free guidance scale {g:g} is above CFG_SCALE_MAX = {CFG_SCALE_MAX:g}: the f16 MFMA "
+                          "operands' rounding grows with the scale and may exceed 1e-3 relative L2; DenoiserEngine.set_precise(True) / "
+                          "MST_PRECISE=1 splits every operand (hi + lo)", stacklevel=3)
 
     def set_trunk_groups(self, on=True):
         """The encoder stack of a sampling step as ONE launch of resident workgroup groups (csrc/mst_trunk.h); bit-identical results."""

@@ -30,6 +30,7 @@ class ClassifierFreeSampleModel(nn.Module):
         if hasattr(m, "mst_engine") and not m._wants_autograd(x):
             eng = m.mst_engine(2 * x.shape[0], x.shape[-1])
             m.mst_prepare(eng, y, True)
+            eng.check_guidance_scale(y['scale'])            # once per scale tensor object (engine.CFG_SCALE_MAX)
             return eng.forward(x, timesteps, scale=y['scale'], cfg=True)
         y_uncond = deepcopy(y)
         y_uncond['uncond'] = True
