@@ -272,6 +272,7 @@ struct mst_engine {
     // several styles (mst_style.h): slot 0 is L[]; slots 1 .. nslots - 1 hold only what sampling reads
     int nslots = 1;
     std::vector<LayerW> slot_w;           // [(slot - 1) * 16 + layer]
+    std::vector<char> slot_loaded;        // [slot]: mst_load_layers_slot has filled it (slot 0: mst_weights_complete decides)
     StyleLayer* style_tab = nullptr;      // [nslots][num_layers] in device memory (pointers fixed when the slots are made)
     f16* style_stage = nullptr;           // one layer's plain f16 matrices: mst_load_layers_slot converts into it, then packs
     std::vector<int> styles;              // slot of every clip of the batch mst_set_styles named (empty: off)
@@ -1180,6 +1181,7 @@ extern "C" int mst_style_slots(mst_engine* e, int32_t n) {
         CHECK(dmalloc(&e->plan_dev, cap));
         e->plan_cap = cap;
     }
+    e->slot_loaded.resize(n, 0);                          // existing slots keep their state
     e->nslots = n;
     return 0;
 }
@@ -1220,6 +1222,7 @@ extern "C" int mst_load_layers_slot(mst_engine* e, int32_t slot, const float* co
         hipLaunchKernelGGL(k_pack_blocks, dim3(128), dim3(256), 0, st, w2, MST_FF, MST_D, MST_FF, w.wsm_2);
         HIPCHECK(hipGetLastError());
     }
+    e->slot_loaded[slot] = 1;
     return 0;
 }
 
@@ -1231,6 +1234,11 @@ extern "C" int mst_set_styles(mst_engine* e, const int32_t* styles_host, int32_t
     for (int i = 0; i < batch; i++)
         if (styles_host[i] < 0 || styles_host[i] >= e->nslots)
             return fail("mst_set_styles: clip %d has style %d outside [0, %d)", i, styles_host[i], e->nslots);
+    for (int i = 0; i < batch; i++) {                        // slot memory is allocated uninitialised: never sample with it
+        const int s = styles_host[i];
+        if (s == 0 ? mst_weights_complete(e) != 0 : !e->slot_loaded[s])
+            return fail("mst_set_styles: clip %d names style slot %d, which was never loaded (mst_load_layers_slot)", i, s);
+    }
     e->styles.assign(styles_host, styles_host + batch);
     return 0;
 }
@@ -2139,6 +2147,11 @@ static int train_check(mst_engine* e, int rows, int S, float p) {
         return fail("train: batch too large for the 32-bit dropout counters");
     return 0;
 }
+// The training stack reads slot 0's weights only: with several styles set it would compute every clip with slot 0.
+static int train_refuse_styles(const mst_engine* e, const char* who) {
+    if (styles_on(e)) return fail("%s: styles are set (mst_set_styles / StyleBank); training runs one stack: mst_set_styles(e, nullptr) first", who);
+    return 0;
+}
 
 extern "C" int64_t mst_train_tape_bytes(const mst_engine* e, int32_t rows, int32_t S) {
     if (!e || rows < 1 || S < 1) return -1;
@@ -2300,6 +2313,7 @@ static int train_stack_forward(mst_engine* e, const Tape& t, int rows, int S, fl
 extern "C" int mst_train_forward(mst_engine* e, const float* h_in, int32_t rows, int32_t S, float p_drop, uint64_t seed,
                                  const uint8_t* key_keep, void* tape, float* h_out, void* stream) {
     CHECK(train_check(e, rows, S, p_drop));
+    CHECK(train_refuse_styles(e, "mst_train_forward"));
     if (!h_in || !tape || !h_out) return fail("mst_train_forward: null argument");
     hipStream_t st = (hipStream_t)stream;
     ON_DEVICE(e->cfg.device);
@@ -2653,6 +2667,7 @@ extern "C" int mst_train_model_forward(mst_engine* e, const float* x, const int6
     if (tape_clips <= 0) { tape_clips = batch; clip0 = 0; }
     if (clip0 < 0 || clip0 + batch > tape_clips) return fail("mst_train_model_forward: clips %d..%d outside a tape of %d", clip0, clip0 + batch, tape_clips);
     CHECK(train_check(e, tape_clips, S, p_drop));
+    CHECK(train_refuse_styles(e, "mst_train_model_forward"));
     if (!(p_pe >= 0.f && p_pe < 1.f)) return fail("mst_train_model_forward: positional-encoding dropout %g outside [0, 1)", (double)p_pe);
     if (!x || !t_idx || !tape || !out) return fail("mst_train_model_forward: null argument");
     hipStream_t st = (hipStream_t)stream;
@@ -2748,6 +2763,7 @@ extern "C" int mst_motion_encoder_forward(mst_engine* e, const float* x, const f
                                           const uint8_t* key_keep, int32_t batch, int32_t frames, float p_drop, float p_pe,
                                           uint64_t seed, void* tape, float* mu_out, void* stream) {
     CHECK(menc_check(e, batch, frames, p_drop, p_pe));
+    CHECK(train_refuse_styles(e, "mst_motion_encoder_forward"));
     if (!x || !mu_query || !sigma_query || !tape || !mu_out) return fail("mst_motion_encoder_forward: null argument");
     hipStream_t st = (hipStream_t)stream;
     ON_DEVICE(e->cfg.device);

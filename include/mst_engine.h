@@ -378,7 +378,9 @@ int mst_load_layers_slot(mst_engine* e, int32_t slot, const float* const* srcs_h
 /* The slot of every clip of the next mst_forward / mst_sample_loop calls (host int32[batch], any order; under CFG a clip's
  * unconditional twin uses the clip's slot).  styles_host = NULL: back to the single-style behaviour.  With more than one slot the
  * calls refuse (and name) every configuration the style-aware kernels do not cover: precise mode, the resident trunk, MST_FUSE_TAIL=0,
- * MST_FUSE_QKV_ATTN other than 1, MST_SMALL_FAST=0, clips of <= 16 or > 207 frames, debug stops, graph replay, profiling. */
+ * MST_FUSE_QKV_ATTN other than 1, MST_SMALL_FAST=0, clips of <= 16 or > 207 frames, debug stops, graph replay, profiling.
+ * A clip naming a slot that mst_load_layers_slot never filled (slot 0: weights incomplete) is refused here.  While styles are set,
+ * mst_train_forward, mst_train_model_forward and mst_motion_encoder_forward refuse: training runs slot 0 only. */
 int mst_set_styles(mst_engine* e, const int32_t* styles_host, int32_t batch, void* stream);
 /* Host-only planner (no GPU): split every tile of `tile_rows` token rows of nclips x S rows into maximal runs of one slot.  Writes
  * {row0, row_lo, row_hi, slot} int32 records to out (at most cap of them); returns their count, or -1 (mst_last_error) if cap is

@@ -10,66 +10,28 @@ import torch
 import mst_amd  # noqa: F401
 from mst_amd import synthetic as syn
 from conftest import SEED, rel_l2
+import style_fixture as sf
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-3
 SHAPES = {"xia": (181, 76), "hml": (263, 196)}
 K = 3
-PRIOR = "motion_enc.mdm_model."
-LP = "seqTransEncoder.layers."
-
-
-def _dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-
-
-_W = {}
+PRIOR, LP = sf.PRIOR, sf.LP
+_dev, cu, _pe = sf.dev, sf.cu, sf.pe
 
 
 def style_weights(tag, s):
-    """Style s: the stack of seed SEED + 1 + s, the prior of SEED (shared by every style)."""
-    if (tag, s) not in _W:
-        F, _ = SHAPES[tag]
-        prior = syn.denoiser_state(SEED, F, layer_prefix=LP, prior_prefix=PRIOR)
-        w = syn.denoiser_state(SEED + 1 + s, F, layer_prefix=LP, prior_prefix=PRIOR)
-        w.update({k: v for k, v in prior.items() if k.startswith(PRIOR)})
-        _W[(tag, s)] = w
-    return _W[(tag, s)]
+    return sf.style_weights(SHAPES[tag][0], s)
 
 
 def _layer_list(w, nl=8):
-    from mst_amd.engine import LAYER_TENSORS
-    return [cu(w[f"{LP}{i}.{k}"]) for i in range(nl) for k in LAYER_TENSORS]
-
-
-_PE = None
-
-
-def _pe():
-    global _PE
-    if _PE is None:
-        _PE = syn.positional_table(5000, 512)
-    return _PE
+    return sf.layer_list(w, nl)
 
 
 def make_engine(tag, max_rows, slots=K):
-    from mst_amd.engine import DenoiserEngine
     F, T = SHAPES[tag]
-    eng = DenoiserEngine(F, T, max_rows, device=_dev())
-    eng.load_state_dict({k: torch.from_numpy(v) for k, v in style_weights(tag, 0).items()}, prior_prefix=PRIOR,
-                        pe=torch.from_numpy(_pe()))
-    if slots > 1:
-        eng.style_slots(slots)
-        for s in range(1, slots):
-            eng.load_layers_slot(s, _layer_list(style_weights(tag, s)))
-    torch.cuda.synchronize()
-    return eng
+    return sf.make_engine(F, T, max_rows, slots)
 
 
 def interleaved(B):
@@ -85,11 +47,7 @@ def _inputs(tag, B):
     return x, t, txt, scale
 
 
-def _schedule():
-    from mst_amd.engine import Schedule
-    from oracle import schedule
-    tab, tmap = schedule.make("cosine", 1000, "")
-    return Schedule(tab, tmap, _dev())
+_schedule = sf.schedule
 
 
 def run(eng, styles, tag, B, cfg, steps):
@@ -133,8 +91,7 @@ def test_one_style_unchanged(tag, B):
 
 
 def _oracle_forward(tag, s, x, t, txt):
-    from oracle import denoiser
-    return denoiser.forward(style_weights(tag, s), _pe(), x, t, txt, prior=PRIOR)
+    return sf.oracle_forward(SHAPES[tag][0], s, x, t, txt)
 
 
 @pytest.mark.parametrize("tag,B", [("xia", 4), ("hml", 16)], ids=["small", "fused"])
@@ -255,3 +212,56 @@ def test_bank_through_the_samplers():
                         cond_fn_with_grad=True)
     with pytest.raises(ValueError, match="outside"):
         d.p_sample_loop(bank, (B, F, 1, T), model_kwargs={"y": {"text_embed": txt, "style": st + 1}}, progress=False)
+
+
+def test_unloaded_slot_is_refused():
+    """A slot that mst_style_slots allocated but mst_load_layers_slot never filled holds uninitialised memory: naming it is refused,
+    and the refused call leaves the engine's styles as they were (nothing runs with that slot).  Growing keeps loaded slots loaded."""
+    tag, B = "xia", 4
+    eng = make_engine(tag, B)                           # slots 1-2 loaded
+    eng.style_slots(4)                                  # slot 3: allocated only
+    x, t, txt, _ = _inputs(tag, B)
+    eng.set_text(txt)
+    eng.set_styles([0, 1, 2, 1])
+    before = eng.forward(x, t)
+    with pytest.raises(RuntimeError, match=r"slot 3, which was never loaded \(mst_load_layers_slot\)"):
+        eng.set_styles([0, 1, 3, 2])
+    with pytest.raises(RuntimeError, match="outside"):                          # the range check comes first
+        eng.set_styles([0, 4, 3, 0])
+    assert torch.equal(eng.forward(x, t), before)
+    eng.load_layers_slot(3, _layer_list(style_weights(tag, 3)))
+    eng.set_styles([0, 1, 3, 2])
+    out = eng.forward(x, t).cpu().numpy()
+    ref = np.asarray(_oracle_forward(tag, 3, x.cpu().numpy()[[2]], t.cpu().numpy()[[2]], txt.cpu().numpy()[[2]]))
+    assert rel_l2(out[[2]], ref) < TOL
+
+
+def test_training_entries_refuse_styles():
+    """The training stack runs slot 0 only: with styles set, mst_train_forward, mst_train_model_forward and mst_motion_encoder_forward
+    refuse; after set_styles(None) they give the bits of an engine that never had slots (dropout 0)."""
+    tag, B = "xia", 2
+    F, T = SHAPES[tag]
+    plain, bank = make_engine(tag, B, slots=1), make_engine(tag, B)
+    x, t, txt, _ = _inputs(tag, B)
+    h = cu(syn.normal(SEED, "sb/train/h", (B, T + 1, 512)))
+    mu_q, sg_q = cu(syn.normal(SEED, "sb/train/mu", (512,))), cu(syn.normal(SEED, "sb/train/sigma", (512,)))
+    x_me = x[..., :T - 1].contiguous()                  # the motion encoder adds 2 query tokens: at most T - 1 frames here
+    keep = torch.ones(B, T + 1, dtype=torch.bool)
+
+    def model_forward(e):
+        e.set_text(txt)
+        return e.train_model_forward(x, t, 0.0, 0.0, 5)[0]
+
+    calls = {"mst_train_forward": lambda e: e.train_forward(h, 0.0, 5)[0],
+             "mst_train_model_forward": model_forward,
+             "mst_motion_encoder_forward": lambda e: e.motion_encoder_forward(x_me, mu_q, sg_q, keep, 0.0, 0.0, 5)[0]}
+    bank.set_text(txt)
+    bank.set_styles([1, 2])
+    for name, fn in calls.items():
+        with pytest.raises(RuntimeError, match=f"{name}: styles are set \\(mst_set_styles / StyleBank\\)"):
+            fn(bank)
+    bank.set_styles(None)
+    for name, fn in calls.items():
+        a, b = fn(plain), fn(bank)
+        torch.cuda.synchronize()
+        assert torch.equal(a, b), name

@@ -12,10 +12,13 @@ def _assignments(n):
         "interleaved": [(0, 1, 1, 2, 0, 2)[i % 6] for i in range(n)],
         "grouped": sorted(i * 3 // n for i in range(n)),
         "uniform": [1] * n,
+        "cycle": [i % 3 for i in range(n)],
+        "odd": [1 if i != n // 2 else 2 for i in range(n)],             # a single clip of another style
+        "pairs": [(i // 2) % 3 for i in range(n)],                        # runs of two
     }
 
 
-@pytest.mark.parametrize("S", [77, 197])
+@pytest.mark.parametrize("S", [18, 33, 41, 77, 197])
 @pytest.mark.parametrize("tile_rows", [16, 32, 48, 64])
 @pytest.mark.parametrize("nclips", [1, 4, 13, 64])
 def test_planner_covers_every_row_once(S, tile_rows, nclips):
@@ -40,6 +43,23 @@ def test_planner_covers_every_row_once(S, tile_rows, nclips):
                 assert a[3] != b[3] and a[2] == b[1], name
         if name == "uniform":
             assert len(seg) == tiles
+
+
+@pytest.mark.parametrize("nclips", [24, 56])
+def test_short_clips_put_several_segments_in_one_tile(nclips):
+    """18-token clips (T = 17), styles cycling: 48- and 64-row tiles each hold >= 3 segments somewhere, so that the GPU cases of
+    tests/test_gpu_style_kernels.py at T = 17 run several workgroups over one tile."""
+    import __graft_entry__ as g
+    g.build()
+    from mst_amd.engine import plan_style_segments
+    styles = _assignments(nclips)["cycle"]
+    for tile_rows in (48, 64):
+        seg = plan_style_segments(styles, 18, tile_rows)
+        per_tile = np.unique(seg[:, 0], return_counts=True)[1]
+        assert per_tile.max() >= 3, (tile_rows, per_tile)
+    odd = [r for r in plan_style_segments(_assignments(nclips)["odd"], 18, 64) if r[3] == 2]
+    c = nclips // 2                                                     # the odd clip: its own segment (two across a tile edge)
+    assert 1 <= len(odd) <= 2 and odd[0][1] == 18 * c and odd[-1][2] == 18 * c + 18, odd
 
 
 def test_planner_reports_a_short_table():
