@@ -382,14 +382,19 @@ class GaussianDiffusion:
         scale = y['scale'] if cfg is not None else None
         sch = self._schedule(img.device)
         x = img.contiguous().float().clone()
+        philox = self.noise_source == "philox"
+        # const_noise (reference :569-572, `_draw`: every clip gets clip 0's noise): the in-kernel draw is keyed by the clip index, so
+        # the philox source then draws ONE clip's numbers with the same generator (philox_normal, key seed + c0, step j) and hands them
+        # to the loop as buffer noise repeated over the batch, in chunks bounded like the torch source's
+        in_kernel = philox and not const_noise
         if not chunked:
             chunk = 1
-        elif self.noise_source == "philox":
+        elif in_kernel:
             # no noise buffer; with an x0-hat dump the dump itself is bounded the same way
             chunk = len(indices) if not want_xstart else max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
         else:
             chunk = max(1, min(int(self.noise_chunk), int(self.noise_chunk_bytes // (x.numel() * 4))))
-        seed = int(th.randint(0, 2 ** 31 - 1, (1,)).item()) if self.noise_source == "philox" else 0
+        seed = int(th.randint(0, 2 ** 31 - 1, (1,)).item()) if philox else 0
         if cfg is not None:
             eng.check_guidance_scale(scale)                 # once per loop (engine.CFG_SCALE_MAX), not per chunk or step
         it = range(0, len(indices), chunk)
@@ -399,8 +404,10 @@ class GaussianDiffusion:
         for c0 in it:
             idx = indices[c0:c0 + chunk]
             noise = None
-            if self.noise_source != "philox":
+            if not philox:
                 noise = th.stack([self._draw(x, const_noise) for _ in idx])
+            elif not in_kernel:
+                noise = th.stack([eng.philox_normal(1, x.shape[-1], seed + c0, j).expand(x.shape) for j in range(len(idx))])
             res = eng.sample_loop(sch, x, idx[0], idx[-1], sampler, eta, cfg=cfg is not None, scale=scale,
                                   mask=mask if mask is not None else nmask, motion=motion, mask_noise=nmask is not None,
                                   clip_denoised=clip_denoised, noise=noise, seed=seed + c0, dump_xstart=want_xstart)

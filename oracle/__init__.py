@@ -9,6 +9,9 @@ tensor math, as the reference does), the algorithm of the reference's per-step d
                        diffusion/respace.py:129-134 ; model/cfg_sampler.py:36-43
   oracle/denoiser.py   model/mdm_forstyledataset.py:387-478,592-625 and the torch
                        nn.TransformerEncoderLayer arithmetic configured at :539-546
+  oracle/philox.py     the engine's OWN in-kernel noise (no reference counterpart: the reference draws th.randn_like):
+                       Philox4x32-10 as published, the uniform mapping, Box-Muller and the counter layout of
+                       include/mst_engine.h, in float64; pinned by Random123's known-answer vectors (tests/test_philox_cpu.py)
 
 Who may import it: only `tests/`, `__graft_entry__.smoke()` and the `cpu_baseline` leg of `bench.py`,
 and there only as the checker / the reported CPU baseline.  Nothing under the product package

@@ -1,0 +1,444 @@
+"""The in-kernel Philox noise (MST_NOISE_PHILOX: what bench.py's headline draws, 1000 times per loop) held to oracle/philox.py.
+
+  a. `mst_philox_normal` against the float64 oracle, EVERY element, over ragged and whole frame counts, every feature width the
+     datasets have, seeds with either key word set, steps up to 2^32 - 1; nothing written behind the tensor.
+  b. every kernel that draws == the same numbers injected as a buffer, bit for bit, sample and x0-hat dump, over the paths, frame
+     counts, samplers, slice plans, guidance, inpainting masks, loop ranges and variants that change how the counter
+     (t >> 2, f, clip + clip0, step) or the component t & 3 is computed.  philox_normal4 (csrc/mst_common.h) has three callers:
+       embed-staged   mst_embed.h   OutItems::noise1        k_embed_out, T % 4 == 0, <= 384 features (early under NX = 1, late under CFG)
+       finish-vector  mst_gemm_dma.h DEpiEmbedOut::finish   T % 4 == 0 in k_gemm_dma (engine precise mode; also MST_EMBED_FAST=0 and
+                                                            more than 384 features, which no test of the suite runs)
+       finish-scalar  mst_gemm_dma.h DEpiEmbedOut::finish   T % 4 != 0, either kernel: its own nrm[t & 3] pick
+     Every row names the trunk path and the drawing site it runs, derived by mirrors of the engine's launch rules (plain_path,
+     draw_site, slices below; the style rows use the style tests' trunk_path), checked against `eng.loop_slices`, and -- where the
+     loop is one slice of plain kernels -- against the kernel families `profile_read` reports for a profiled run that must equal the
+     plain one bit for bit.
+  c. one DDPM step in closed form: (sample - posterior mean(x0-hat, x)) / sigma == the ORACLE's normals (not mst_philox_normal's).
+  d. the drop-in boundary under noise_source = "philox": chunk seeds, loop-to-loop seeds, const_noise.
+
+Measured on an MI355X (docs/LAB_NOTES.md, "Philox noise against the float64 oracle"): see MAX_DEV_MEASURED below; the module
+runs in 6.2 s where tests/test_gpu_edges.py takes 8.6 s on the same box."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import mst_amd  # noqa: F401
+import mst_amd.synthetic as syn
+from conftest import rel_l2  # noqa: F401  (the modules' common import; every comparison here is exact or absolute)
+from oracle import philox, schedule
+
+pytestmark = pytest.mark.gpu
+SEED = 77
+HI = 1 << 32
+
+# (a) worst |mst_philox_normal - oracle| over exactly the cases of test_philox_normal_equals_the_oracle_elementwise, MI355X.  The
+# integer part (generator, 24-bit uniforms) is exact; this is v_log_f32 / v_sqrt_f32 / v_sin_f32 / v_cos_f32 against float64
+# libm at radii up to sqrt(48 ln 2) = 5.77.  The bar is four times that (margin for seeds not in the list) and may not pass 1e-4.
+MAX_DEV_MEASURED = 8.8e-7                # 8.725e-07, at (64, 263, 196); 7.1e-07 within 2^-12 revolutions of angle 0, 1/4, 1/2, 3/4
+BAR_A = 4 * MAX_DEV_MEASURED
+assert BAR_A <= 1e-4
+
+
+def dev():
+    return torch.device("cuda:0")
+
+
+def cu(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
+
+
+_W = {}
+
+
+def weights(F):
+    if F not in _W:
+        _W[F] = ({k: torch.from_numpy(v) for k, v in syn.denoiser_state(SEED, F).items()}, torch.from_numpy(syn.positional_table(5000, 512)))
+    return _W[F]
+
+
+def make(F, T, rows):
+    from mst_amd.engine import DenoiserEngine
+    eng = DenoiserEngine(F, T, rows, device=dev())
+    w, pe = weights(F)
+    eng.load_state_dict(w, pe=pe)
+    return eng
+
+
+_SCH = {}
+
+
+def sched(respacing=""):
+    from mst_amd.engine import Schedule
+    if respacing not in _SCH:
+        tab, tmap = schedule.make("cosine", 1000, respacing)
+        _SCH[respacing] = (Schedule(tab, tmap, dev()), tab)
+    return _SCH[respacing]
+
+
+# ------------------------------------------------------------------------------ a. mst_philox_normal against the oracle
+SHAPES_A = [(1, 24, 1), (2, 24, 3), (1, 181, 76), (3, 190, 75), (2, 181, 61), (2, 263, 6), (1, 263, 223), (64, 263, 196)]   # T % 4 = 1, 3, 0, 3, 1, 2, 3, 0
+SEEDS_A = [0, 1234, 5 * HI, 7 * HI + 99, 2 ** 63 - 1]
+STEPS_A = [0, 1, 999, 2 ** 32 - 1]
+HEADLINE_A = [(s, 0) for s in SEEDS_A] + [(1234, j) for j in STEPS_A[1:]]       # the 3.3 M-value shape: every seed, every step, not the product
+SENTINEL = 12345.5
+NEAR = 2.0 ** -12                        # |angle uniform - k / 4| below this many revolutions: where v_sin / v_cos cross zero
+
+
+def gpu_normal(B, F, T, seed, step):
+    """mst_philox_normal through the C ABI into a buffer with a sentinel tail; returns ([B, F, T] float64, tail intact?)."""
+    from mst_amd import _native as N
+    n, tail = B * F * T, 1024
+    buf = torch.full((n + tail,), SENTINEL, dtype=torch.float32, device=dev())
+    N.check(N.lib().mst_philox_normal(N.ptr(buf), B, F, T, C.c_uint64(seed), C.c_uint32(step), N.stream_ptr(dev())))
+    torch.cuda.synchronize()
+    host = buf.cpu().numpy()
+    return host[:n].astype(np.float64).reshape(B, F, T), bool((host[n:] == SENTINEL).all())
+
+
+@pytest.mark.parametrize("B,F,T", SHAPES_A, ids=[f"B{b}-F{f}-T{t}" for b, f, t in SHAPES_A])
+def test_philox_normal_equals_the_oracle_elementwise(B, F, T):
+    """Measured maximum |kernel - oracle| over exactly these cases on an MI355X: 8.725e-07 (at (64, 263, 196); 2.9e-07 .. 7.8e-07
+    at the smaller shapes), and 7.148e-07 over the 51 208 elements of that shape whose angle uniform lies within 2^-12 revolutions
+    of 0, 1/4, 1/2, 3/4, where v_sin_f32 / v_cos_f32 cross zero: no worse there.  That is 1.3 float32 ulp at the largest radius
+    (sqrt(48 ln 2) = 5.77, ulp 4.8e-07).  Bar: 4 x 8.8e-07 = 3.5e-06, 28 times below the 1e-4 the bar may not pass
+    (docs/LAB_NOTES.md, "Philox noise against the float64 oracle").  A wrong stream (round count, key schedule, counter word order,
+    component pick, sin / cos swapped) differs by O(1) on almost every element."""
+    cases = HEADLINE_A if B * F * T > 1 << 20 else [(s, j) for s in SEEDS_A for j in STEPS_A]
+    worst, worst_near, n_near = 0.0, 0.0, 0
+    for seed, step in cases:
+        got, tail_ok = gpu_normal(B, F, T, seed, step)
+        want, _, ang = philox.planes(B, F, T, seed, step)
+        assert tail_ok, f"seed {seed} step {step}: written behind [B, F, T]"
+        assert np.isfinite(got).all()
+        d = np.abs(got - want)
+        near = np.abs(ang * 4.0 - np.round(ang * 4.0)) < 4.0 * NEAR                    # the oracle's own uniforms pick them
+        worst, n_near = max(worst, float(d.max())), n_near + int(near.sum())
+        if near.any():
+            worst_near = max(worst_near, float(d[near].max()))
+        assert d.max() <= BAR_A, (seed, step, float(d.max()), np.unravel_index(int(d.argmax()), d.shape))
+    print(f"\nphilox_normal vs oracle B{B} F{F} T{T}: max |dev| {worst:.3e} over {len(cases)} (seed, step) cases; "
+          f"near angle 0, 1/4, 1/2, 3/4 ({n_near} elements): {worst_near:.3e}; bar {BAR_A:.1e}")
+
+
+# ------------------------------------------------------------------------------ b. every kernel that draws
+SMALL_M, SMALL_LN_M = 1900, 512          # csrc/mst_engine.hip defaults (MST_SMALL_M, MST_SMALL_LN_M)
+
+
+def plain_path(rows, T, small_m=SMALL_M, precise=False):
+    """Mirror of run_trunk for `rows` transformer rows of T frames (one slice's launch)."""
+    M = rows * (T + 1)
+    if not (precise or (small_m > 0 and M <= small_m)):
+        return "fused-large-tile"
+    if precise or T <= 16:
+        return "small-tile-hi-lo"        # every activation as hi + lo: engine precise mode, or clips of <= 16 frames
+    return "small-launch-ln-in-gemm" if M <= SMALL_LN_M else "small-tile"
+
+
+def draw_site(F, T, cfg, precise=False):
+    """Mirror of launch_out_nt / k_embed_out's `staged` / DEpiEmbedOut::finish's `vec`: which caller of philox_normal4 draws."""
+    nbw = (F + 127) // 128
+    kernel = "k_embed_out" if not precise and not (cfg and nbw == 4) else "k_gemm_dma"        # (MST_EMBED_FAST at its default)
+    if T % 4:
+        return kernel + ":finish-scalar"
+    return "k_embed_out:embed-staged" if kernel == "k_embed_out" and nbw <= 3 else kernel + ":finish-vector"
+
+
+def slices(B, T, cfg, streams=0, small_m=SMALL_M, trunk=False, precise=False):
+    """Mirror of loop_slices_for + enqueue_step's split: [(first clip, clips)] per slice."""
+    rows = (2 if cfg else 1) * B
+    M = rows * (T + 1)
+    small_launch = small_m > 0 and M <= small_m
+    n = streams
+    if n == 0 and trunk and (T + 16) // 16 == 13 and not small_launch:
+        n = 1
+    elif n == 0:
+        small = precise or small_launch
+        tiles = (M + 63) // 64
+        waves = (tiles + 255) // 256
+        n = 3 if small else min(waves, 3)
+        if not small and waves == 1 and tiles >= 192:
+            n = 3
+    while n > 1 and rows // n < 8:
+        n -= 1
+    per = -(-B // n)
+    return [(c0, min(per, B - c0)) for c0 in range(0, B, per)]
+
+
+FAMILIES = {"fused-large-tile": {"qkv_attention_fused", "layer_tail_fused"},
+            "small-tile": {"qkv_gemm", "attention", "outproj_ln_gemm", "ffn1_gelu_gemm", "ffn2_ln_gemm"}}
+TRUNK_FAMILIES = FAMILIES["fused-large-tile"] | FAMILIES["small-tile"]
+FAMILIES["small-tile-hi-lo"] = FAMILIES["small-launch-ln-in-gemm"] = FAMILIES["small-tile"]
+
+
+def mask_of(kind, B, F, T):
+    if kind == "root":
+        return syn.root_horizontal_mask(B, F, T)
+    m = np.zeros((B, F, 1, T), np.float32)                   # tests/test_gpu_edges.py: every third feature, frames 0 .. T / 2
+    m[:, ::3, :, : max(1, T // 2)] = 1
+    return m
+
+
+def row(id, F, T, B, sampler="ddpm", eta=0.0, cfg=False, mask=None, rng=(4, 0), env=None, expect=None, site=None, nsl=1, **variant):
+    return pytest.param(dict(F=F, T=T, B=B, sampler=sampler, eta=eta, cfg=cfg, mask=mask, rng=rng, env=env or {}, expect=expect,
+                             site=site, nsl=nsl, **variant), id=id)
+
+
+EMB, VEC, SCA = "k_embed_out:embed-staged", "k_gemm_dma:finish-vector", "k_embed_out:finish-scalar"
+ROWS = [
+    # ---- large-tile fused path (k_qkv_attention + k_layer_tail per layer)
+    row("fused-T196-B10-ddpm-1slice-embed-staged", 263, 196, 10, expect="fused-large-tile", site=EMB),
+    row("fused-T196-B25-ddim.5-3slices-9+9+7-root-mask-tend996-embed-staged", 263, 196, 25, "ddim", 0.5, mask="root", rng=(999, 996),
+        env={"MST_STREAMS": 3, "MST_SMALL_M": 0}, expect="fused-large-tile", site=EMB, nsl=3),
+    row("fused-T196-B17-ddpm-cfg-2slices-9+8-third-mask-embed-staged-late", 263, 196, 17, cfg=True, mask="third",
+        env={"MST_STREAMS": 2, "MST_SMALL_M": 0}, expect="fused-large-tile", site=EMB, nsl=2),
+    row("fused-T223-B9-ddpm-finish-scalar", 263, 223, 9, rng=(500, 498), expect="fused-large-tile", site=SCA),
+    row("fused-T75-B26-ddim.5-cfg-finish-scalar", 190, 75, 26, "ddim", 0.5, cfg=True, mask="root", rng=(3, 0), expect="fused-large-tile", site=SCA),
+    # ---- small-tile path (<= 1900 token rows per launch)
+    row("small-T76-B17-ddpm-2slices-9+8-root-mask-continued", 181, 76, 17, mask="root", rng=(6, 4), expect="small-tile", site=EMB, nsl=2,
+        then=(3, 0)),
+    row("small-T75-B12-ddim.5-third-mask-finish-scalar", 190, 75, 12, "ddim", 0.5, mask="third", expect="small-tile", site=SCA),
+    row("small-T196-B5-ddim0-noise-has-no-effect", 263, 196, 5, "ddim", 0.0, rng=(999, 997), expect="small-tile", site=EMB),
+    row("small-T75-B17-ddpm-2slices-9+8-finish-scalar", 190, 75, 17, mask="third", expect="small-tile", site=SCA, nsl=2),
+    row("small-T76-B25-ddpm-3slices-9+9+7-tend", 181, 76, 25, rng=(700, 697), env={"MST_STREAMS": 3}, expect="small-tile", site=EMB, nsl=3),
+    # ---- small-launch path (<= 512 token rows: LayerNorm inside the consuming GEMM)
+    row("launch-T61-B3-ddpm-finish-scalar", 150, 61, 3, expect="small-launch-ln-in-gemm", site=SCA),
+    row("launch-T76-B2-ddim.5-root-mask-tend", 181, 76, 2, "ddim", 0.5, mask="root", rng=(800, 797), expect="small-launch-ln-in-gemm", site=EMB),
+    row("launch-T76-B3-ddpm-cfg", 181, 76, 3, cfg=True, mask="root", expect="small-launch-ln-in-gemm", site=EMB),
+    # ---- clips of <= 16 frames (hi + lo activations)
+    row("short-T5-B2-ddpm-third-mask-finish-scalar", 181, 5, 2, mask="third", expect="small-tile-hi-lo", site=SCA),
+    row("short-T1-B2-ddim.5-finish-scalar", 24, 1, 2, "ddim", 0.5, expect="small-tile-hi-lo", site=SCA),
+    row("short-T16-B3-ddpm-embed-staged", 263, 16, 3, expect="small-tile-hi-lo", site=EMB),
+    # ---- engine precise mode: the ring GEMM's epilogue draws (k_gemm_dma)
+    row("precise-T76-B2-ddpm-finish-vector", 181, 76, 2, mask="root", expect="small-tile-hi-lo", site=VEC, precise=True),
+    row("precise-T196-B3-ddim.5-finish-vector", 263, 196, 3, "ddim", 0.5, rng=(999, 997), expect="small-tile-hi-lo", site=VEC, precise=True),
+    row("precise-T76-B17-ddpm-2slices-9+8-finish-vector", 181, 76, 17, rng=(300, 298), expect="small-tile-hi-lo", site=VEC, nsl=2, precise=True),
+    row("precise-T61-B2-ddim.5-finish-scalar", 150, 61, 2, "ddim", 0.5, expect="small-tile-hi-lo", site="k_gemm_dma:finish-scalar", precise=True),
+    # ---- variants, each on its own
+    row("styles-2slots-interleaved-T76-B12-ddpm", 181, 76, 12, mask="root", expect="style:small-ntb4-ln", site=EMB, styles=2),
+    row("styles-2slots-interleaved-T75-B5-ddim.5-finish-scalar", 181, 75, 5, "ddim", 0.5, expect="style:small-ntb1-lnf", site=SCA, styles=2),
+    row("trunk-resident-T196-B12-ddpm-root-mask", 263, 196, 12, mask="root", rng=(5, 0), expect="fused-large-tile", site=EMB, trunk=True),
+    row("graph-replay-T76-B17-ddpm-2slices-7steps", 181, 76, 17, mask="root", rng=(6, 0), env={"MST_GRAPH": 1, "MST_GRAPH_STEPS": 2},
+        expect="small-tile", site=EMB, nsl=2, graph=True),
+]
+
+
+def run_loop(eng, sch, c, x0, t_start, t_end, scale, mask, motion, **noise):
+    from mst_amd.engine import SAMPLER_DDPM, SAMPLER_DDIM
+    out, dump = eng.sample_loop(sch, x0.clone(), t_start, t_end, SAMPLER_DDIM if c["sampler"] == "ddim" else SAMPLER_DDPM, c["eta"],
+                                cfg=c["cfg"], scale=scale, mask=mask, motion=motion, mask_noise=mask is not None, dump_xstart=True, **noise)
+    torch.cuda.synchronize()
+    return out, dump
+
+
+@pytest.mark.parametrize("c", ROWS)
+def test_in_kernel_draw_equals_the_same_numbers_injected(c, monkeypatch):
+    """One loop with `seed=`, one with `noise=` stacked from philox_normal(B, T, seed, j): sample and x0-hat dump bit for bit.  The
+    row id names the trunk path, the slice plan and the drawing site; the first assertions prove them from the launch rules."""
+    F, T, B, cfg = c["F"], c["T"], c["B"], c["cfg"]
+    for k, v in c["env"].items():
+        monkeypatch.setenv(k, str(v))
+    env = c["env"]
+    styles, trunk, precise = c.get("styles", 0), c.get("trunk", False), c.get("precise", False)
+    # -- which kernels this row runs, from the launch rules
+    sl = slices(B, T, cfg, env.get("MST_STREAMS", 0), env.get("MST_SMALL_M", SMALL_M), trunk, precise)
+    assert len(sl) == c["nsl"], sl
+    mult = 2 if cfg else 1
+    if styles:
+        from test_gpu_style_kernels import trunk_path
+        paths = {"style:" + trunk_path(mult * nb, T, slices=len(sl)) for _, nb in sl}
+    else:
+        paths = {plain_path(mult * nb, T, env.get("MST_SMALL_M", SMALL_M), precise) for _, nb in sl}
+    assert paths == {c["expect"]}, paths
+    assert draw_site(F, T, cfg, precise) == c["site"]
+    if styles:
+        import style_fixture as sf
+        eng = sf.make_engine(F, T, mult * B, styles)
+    else:
+        eng = make(F, T, mult * B)
+    if precise:
+        eng.set_precise(True)
+    if trunk:
+        eng.set_trunk_groups(True)
+    assert eng.loop_slices(B, cfg, T) == len(sl)
+    sch, _ = sched()
+    shape = (B, F, 1, T)
+    x0 = cu(syn.normal(SEED, "nb/x", shape))
+    txt = cu(syn.normal(SEED, "nb/txt", (B, 512)))
+    scale = cu(np.linspace(1.0, 3.0, B).astype(np.float32)) if cfg else None           # per-clip scales, up to CFG_SCALE_MAX
+    mask = motion = None
+    if c["mask"]:
+        mask, motion = cu(mask_of(c["mask"], B, F, T)), cu(syn.normal(SEED, "nb/motion", shape))
+    eng.set_text(txt, cfg=cfg)
+    if styles:
+        eng.set_styles([i % styles for i in range(B)])
+    seed = 1234 + 3 * HI                                                                 # both key words in use
+    x, checked = x0, 0
+    for t_start, t_end in [c["rng"]] + ([c["then"]] if "then" in c else []):          # `then`: a second call continuing from the first
+        n = t_start - t_end + 1
+        a, da = run_loop(eng, sch, c, x, t_start, t_end, scale, mask, motion, seed=seed)
+        nz = torch.stack([eng.philox_normal(B, T, seed, j) for j in range(n)])         # step counter: 0 .. n - 1 in EVERY call
+        b, db = run_loop(eng, sch, c, x, t_start, t_end, scale, mask, motion, noise=nz)
+        assert torch.isfinite(a).all()
+        assert torch.equal(a, b), f"sample: {int((a != b).sum())} of {a.numel()} elements differ, max {float((a - b).abs().max()):.3e}"
+        assert torch.equal(da, db), f"x0-hat dump: {int((da != db).sum())} elements differ"
+        other, _ = run_loop(eng, sch, c, x, t_start, t_end, scale, mask, motion, seed=seed + 1)
+        if c["sampler"] == "ddim" and c["eta"] == 0.0:
+            assert torch.equal(a, other)                                                 # eta = 0: sigma = 0, the draw must not reach the sample
+        else:
+            free = torch.ones_like(a, dtype=torch.bool) if mask is None else mask == 0
+            assert float((a != other)[free].float().mean()) > 0.99                       # ... and otherwise it must: the rows above compare noise
+        if mask is not None:
+            m = mask.bool()
+            for o in list(da) + list(db) + ([a, b] if t_end == 0 else []):               # (x_{t-1} of an index > 0 still holds its share of x_t)
+                assert torch.equal(o[m], motion[m])                                      # masked entries bit-exact under both noise modes
+        if trunk:
+            eng.trunk_check()
+        # -- a loop that is one slice of plain kernels: the families an instrumented run launches, and that run equals this one
+        if len(sl) == 1 and not (styles or trunk or c.get("graph")):
+            eng.profile(True, 1)
+            try:
+                p, dp = run_loop(eng, sch, c, x, t_start, t_end, scale, mask, motion, seed=seed)
+                fams = {k for k, v in eng.profile_read().items() if v[1]}
+            finally:
+                eng.profile(False)
+            assert torch.equal(a, p) and torch.equal(da, dp)
+            assert FAMILIES[c["expect"]] | {"embed_out_step"} <= fams and not fams & (TRUNK_FAMILIES - FAMILIES[c["expect"]]), fams
+            checked += 1
+        x, seed = a, seed + 7
+    if trunk:
+        eng.set_trunk_groups(False)
+    print(f"\n{c['expect']} / {c['site']} / slices {sl}" + (" / families confirmed by a profiled run" if checked else ""))
+
+
+# ------------------------------------------------------------------------------ c. one step in closed form
+def test_one_ddpm_step_recovers_the_oracle_normals():
+    """x_{t-1} = c1 x0-hat + c2 x_t + sigma_t n on the fused path (10 clips x 197 tokens, k_embed_out's staged epilogue): with the
+    kernel's own x0-hat (the dump), n = (x_{t-1} - c1 x0-hat - c2 x_t) / sigma_t in float64 must be oracle.philox.normal.
+    Measured on an MI355X at t = 900 (sigma 0.1405): max |n - oracle| 2.8e-06 where the bound below allows 1.2e-05."""
+    from mst_amd.engine import SAMPLER_DDPM
+    F, T, B, t, seed = 263, 196, 10, 900, 99 + 2 * HI
+    assert plain_path(B, T) == "fused-large-tile" and draw_site(F, T, False) == EMB and len(slices(B, T, False)) == 1
+    eng = make(F, T, B)
+    sch, tab = sched()
+    x = cu(syn.normal(SEED, "cf/x", (B, F, 1, T)))
+    eng.set_text(cu(syn.normal(SEED, "cf/txt", (B, 512))))
+    out, dump = eng.sample_loop(sch, x.clone(), t, t, SAMPLER_DDPM, mask_noise=False, seed=seed, dump_xstart=True)
+    torch.cuda.synchronize()
+    c1, c2 = float(tab["posterior_mean_coef1"][t]), float(tab["posterior_mean_coef2"][t])
+    sigma = math.exp(0.5 * float(tab["posterior_log_variance_clipped"][t]))
+    s, p, xt = (v.double().cpu().numpy().reshape(B, F, T) for v in (out, dump[0], x))
+    want = philox.normal(B, F, T, seed, 0)                                               # a one-step call: step counter 0
+    got = (s - (c1 * p + c2 * xt)) / sigma
+    # fp32 cancellation, from the magnitudes: the kernel rounds c1 and c2 to float32 (eps each on its product), rounds c1 p, c2 x (or
+    # their fma), the mean, sigma n and the sum (eps = 2^-24 of each), and makes sigma as expf(0.5f * float32(logvar)): logvar's
+    # rounding (|logvar| eps / 2 relative) plus 2 ulp of expf, bounded by 8 eps on sigma n.  All of it is divided by sigma.
+    eps = 2.0 ** -24
+    bound = BAR_A + eps * (2 * np.abs(c1 * p) + 2 * np.abs(c2 * xt) + np.abs(c1 * p + c2 * xt) + 9 * np.abs(sigma * want) + np.abs(s)) / sigma
+    d = np.abs(got - want)
+    print(f"\nclosed form at t = {t}: sigma {sigma:.4f}, max |n - oracle| {d.max():.3e}, bound there {bound.ravel()[d.argmax()]:.3e} "
+          f"(largest bound {bound.max():.3e}); worst ratio {float((d / bound).max()):.3f}")
+    assert bound.max() < 2e-4                                                            # the bound itself stays far below the O(1) of a wrong stream
+    assert (d <= bound).all(), (float(d.max()), np.unravel_index(int((d / bound).argmax()), d.shape))
+
+
+# ------------------------------------------------------------------------------ d. the drop-in boundary
+def _boundary(B):
+    from test_gpu_boundary import F as FB, PROMPTS, T as TB, build
+    c = build()
+    shp = (B, FB, 1, TB)
+    x = cu(syn.normal(SEED, "bd/x", shp))
+    mask = cu(syn.root_horizontal_mask(B, FB, TB))
+    motion = cu(syn.normal(SEED, "bd/motion", shp))
+    y = {"y": {"text": [PROMPTS[i % 2] for i in range(B)], "mask": torch.ones(B, 1, 1, TB, device=dev()),
+               "inpainting_mask": mask, "inpainted_motion": motion}}
+    return c, shp, x, y
+
+
+@pytest.fixture
+def philox_source():
+    from test_gpu_boundary import build
+    c = build()
+    for k in ("ddim", "r100"):
+        c[k].noise_source = "philox"
+    yield c
+    for k in ("ddim", "r100"):
+        c[k].noise_source = "torch"
+        c[k].__dict__.pop("noise_chunk_bytes", None)
+
+
+def test_boundary_chunks_take_seed_plus_first_index_and_restart_the_step_counter(philox_source):
+    """`_engine_loop` with an x0-hat dump runs `noise_chunk_bytes // bytes(x)` indices per native call; chunk c0 is keyed
+    `seed + c0` and counts its steps from 0.  By that code a chunked loop is NOT the single-chunk loop (which draws (seed, step j)
+    where the chunked one draws (seed + c0, step j - c0)): only the first chunk coincides.  Both statements are asserted."""
+    from mst_amd.engine import SAMPLER_DDPM
+    c, shp, x, y = _boundary(2)
+    d, m = c["ddim"], c["m"]
+    n_idx, per = 20, 7                                                                   # the whole ddim20 process, indices 19 .. 0, in chunks of 7, 7, 6
+    d.noise_chunk_bytes = per * x.numel() * 4
+    torch.manual_seed(5)
+    dump = d.p_sample_loop(m, shp, noise=x.clone(), clip_denoised=False, model_kwargs=y, dump_all_xstart=True)
+    assert len(dump) == n_idx
+    torch.manual_seed(5)
+    seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())                               # the loop's only draw from torch
+    eng = m.mst_engine(2, shp[-1])
+    m.mst_prepare(eng, y["y"], False)
+    sch = d._schedule(dev())
+    mk, mo = y["y"]["inpainting_mask"], y["y"]["inpainted_motion"]
+    xs, mine = x.clone(), []
+    idx = list(range(n_idx))[::-1]
+    chunks = [idx[c0:c0 + per] for c0 in range(0, n_idx, per)]
+    assert len(chunks) >= 3
+    for k, ch in enumerate(chunks):
+        _, dd = eng.sample_loop(sch, xs, ch[0], ch[-1], SAMPLER_DDPM, mask=mk, motion=mo, mask_noise=d.inpainting_noise,
+                                seed=seed + k * per, dump_xstart=True)
+        mine += list(dd)
+    assert all(torch.equal(u, v) for u, v in zip(dump, mine))
+    # the single-chunk loop: the same first chunk, other numbers behind it
+    d.noise_chunk_bytes = 1 << 30
+    torch.manual_seed(5)
+    single = d.p_sample_loop(m, shp, noise=x.clone(), clip_denoised=False, model_kwargs=y, dump_all_xstart=True)
+    assert all(torch.equal(u, v) for u, v in zip(dump[:per + 1], single[:per + 1]))   # x0-hat of index j sees the noise of the steps before it
+    free = mk == 0
+    assert all(float((u != v)[free].float().mean()) > 0.99 for u, v in zip(dump[per + 1:], single[per + 1:]))
+
+
+def test_boundary_loops_draw_a_new_key_per_loop_and_repeat_under_the_same_torch_seed(philox_source):
+    c, shp, x, y = _boundary(2)
+    kw = dict(noise=x.clone(), clip_denoised=False, model_kwargs=y, skip_timesteps=14)
+    torch.manual_seed(11)
+    a = c["ddim"].p_sample_loop(c["m"], shp, **kw)
+    b = c["ddim"].p_sample_loop(c["m"], shp, **kw)                                       # no reseeding: another key
+    torch.manual_seed(11)
+    a2 = c["ddim"].p_sample_loop(c["m"], shp, **kw)
+    free = y["y"]["inpainting_mask"] == 0
+    assert torch.equal(a, a2)
+    assert float((a != b)[free].float().mean()) > 0.99
+
+
+@pytest.mark.parametrize("source", ["torch", "philox"])
+def test_boundary_const_noise_gives_every_clip_clip_0s_noise(philox_source, source):
+    """const_noise=True (reference `p_sample`: noise[[0]].repeat(B)): four clips with identical start, text and inpainting inputs must
+    come out bitwise equal.  The philox source honours the flag by drawing ONE clip's numbers with philox_normal (key seed + c0,
+    step j) and passing them as buffer noise repeated over the batch; before this was written it ignored the flag and every clip
+    got its own in-kernel draw.  The torch source is the control: the same inputs, the reference's own `_draw`."""
+    from test_gpu_boundary import PROMPTS
+    c, shp, x, y = _boundary(4)
+    d = c["r100"]
+    d.noise_source = source
+    rep = lambda v: v[:1].repeat(4, 1, 1, 1).contiguous()
+    y = {"y": {**y["y"], "text": PROMPTS[:1] * 4, "inpainting_mask": rep(y["y"]["inpainting_mask"]), "inpainted_motion": rep(y["y"]["inpainted_motion"])}}
+    torch.manual_seed(3)
+    out = d.p_sample_loop(c["m"], shp, noise=rep(x), clip_denoised=False, model_kwargs=y, skip_timesteps=94, const_noise=True)
+    assert torch.isfinite(out).all()
+    for i in range(1, 4):
+        assert torch.equal(out[i], out[0]), f"clip {i} differs from clip 0 in {int((out[i] != out[0]).sum())} elements"
+    torch.manual_seed(3)
+    plain = d.p_sample_loop(c["m"], shp, noise=rep(x), clip_denoised=False, model_kwargs=y, skip_timesteps=94)
+    assert not torch.equal(plain[1], plain[0])                                           # without the flag the clips do get their own noise
+    if source == "philox":
+        assert torch.equal(plain[0], out[0])                                             # clip 0's numbers are what every clip got
+        with pytest.raises(NotImplementedError):
+            c["ddim"].ddim_sample_loop(c["m"], shp, noise=rep(x), clip_denoised=False, model_kwargs=y, const_noise=True)
