@@ -124,6 +124,24 @@ def _mask_cond(module, cond, force_mask=False):
     return cond
 
 
+def _deepcopy_without_engines(module, memo):
+    """copy.deepcopy of a module that may have run natively.  Its `__dict__` then holds `_mst_*` entries: the engines (ctypes handles
+    on device memory -- the default copy walks into them and raises "ctypes objects containing pointers cannot be pickled"; a copy
+    that shared a handle would free it twice), the recorded parameter versions, the gradient sink and the chain's accumulators, all of
+    them caches tied to the ORIGINAL's parameters.  The copy takes everything else, as the default does, and starts without them: its
+    first native call builds engines of its own from its own parameters.  Only the precise-mode switch is a setting and is kept."""
+    import copy
+    new = module.__class__.__new__(module.__class__)
+    memo[id(module)] = new
+    for k, v in module.__dict__.items():
+        if not k.startswith("_mst_") or k == "_mst_precise":
+            new.__dict__[k] = copy.deepcopy(v, memo)
+    for m in new.modules():               # (plain submodules carry caches too: the encoder's `_mst_stack_params`)
+        for k in [k for k in m.__dict__ if k.startswith("_mst_") and k != "_mst_precise"]:
+            del m.__dict__[k]
+    return new
+
+
 class _EngineHost:
     """Mixin: lazily built native engines for a module that owns (or borrows) an MDM-shaped
     parameter set.  `_engine_sources()` -> (layer_prefix, prior_prefix, parameters to watch)."""
@@ -143,6 +161,9 @@ class _EngineHost:
             eng = _eng.DenoiserEngine(self.input_feats, frames_cap, rows_cap, num_layers=self.num_layers, device=dev,
                                       latent_dim=self.latent_dim, num_heads=self.num_heads, ff_size=self.ff_size,
                                       clip_dim=self.clip_dim)
+            precise = self.__dict__.get("_mst_precise")
+            if precise is not None:          # the module's switch (set_precise) outlives the engine it was first applied to
+                eng.set_precise(precise)     # (before the first upload: the weights go up once, with their lo halves)
             ent = cache[key] = {"eng": eng, "rows": rows_cap, "frames": frames_cap, "version": None}
         src = self.__dict__.get("_mst_sources")          # (layer prefix, prior prefix, parameters to watch): built once;
         if src is None:                                  # Parameter objects survive .to() / load_state_dict / optimizer steps
@@ -163,6 +184,32 @@ class _EngineHost:
                 eng.load_state_dict(sd, layer_prefix=lp, prior_prefix=pp)
             ent["version"] = version
         return ent["eng"]
+
+    def mst_weights_changed(self):
+        """Tell the module that its parameters were written in a way the version watch cannot see: through `.data`
+        (`p.data.copy_()`, `p.data.mul_()`, `p.data.normal_()` leave both `p._version` and `p.data_ptr()` as they were) or through
+        a raw pointer.  Drops the recorded versions of every engine of this module and of every engine host inside it (the style
+        denoiser's motion encoder and prior read the same frozen tensors), so each uploads all its tensors again at its next call;
+        a `StyleBank` that holds this module uploads its slot again as well.  Nothing is compared or summed on the hot path."""
+        for m in self.modules():
+            if isinstance(m, _EngineHost):
+                for ent in m.__dict__.get("_mst_engines", {}).values():
+                    ent["version"] = None
+                m.__dict__["_mst_epoch"] = m.__dict__.get("_mst_epoch", 0) + 1
+
+    def set_precise(self, on=True):
+        """Precise mode (`DenoiserEngine.set_precise`) for every engine THIS module's calls run on, now and later: its own engine, the
+        one rebuilt for a larger batch or a longer clip, the chained calls' side engine, and the engine of a `StyleBank` whose member 0
+        it is (the style-aware kernels have no precise variant: a bank call with the switch on raises, it does not fall back).
+        Engine hosts nested inside it -- the style denoiser's frozen motion encoder and prior -- keep their own switch: precise mode
+        is the sampling path's, and they sample only when called on their own (`model.motion_enc.mdm_model.set_precise(True)`).
+        `mst_weights_changed()` does walk them, because they read the same tensors."""
+        self.__dict__["_mst_precise"] = bool(on)
+        for ent in self.__dict__.get("_mst_engines", {}).values():
+            ent["eng"].set_precise(on)
+
+    def __deepcopy__(self, memo):
+        return _deepcopy_without_engines(self, memo)
 
     def _layer_param_index(self, params):
         """(indices of the encoder stack's tensors inside `params`, those tensors in the engine's layer order), or None when a stack

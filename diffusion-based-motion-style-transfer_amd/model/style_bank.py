@@ -72,11 +72,22 @@ class StyleBank(nn.Module):
             state["eng"] = eng
         for i in range(1, K):
             params = stack_parameters(self.members[i].seqTransEncoder)
-            version = tuple(p._version for p in params) + tuple(p.data_ptr() for p in params)
+            # (the member's epoch: its `mst_weights_changed()` count -- writes through `.data` move neither version nor pointer)
+            version = (self.members[i].__dict__.get("_mst_epoch", 0),) + tuple(p._version for p in params) + tuple(p.data_ptr() for p in params)
             if state.get(i) != version:
                 eng.load_layers_slot(i, [p.detach().float().contiguous() for p in params])
                 state[i] = version
         return eng
+
+    def mst_weights_changed(self):
+        """Every member's `mst_weights_changed()`: after a write through `.data` (invisible to the version watch) the bank's engine
+        uploads slot 0 in full and every other slot's stack again at its next call."""
+        for m in self.members:
+            m.mst_weights_changed()
+
+    def __deepcopy__(self, memo):
+        from .mdm_forstyledataset import _deepcopy_without_engines
+        return _deepcopy_without_engines(self, memo)
 
     def _styles(self, y, bs, device):
         st = None if y is None else y.get('style')
