@@ -300,11 +300,18 @@ __device__ __forceinline__ void philox_normal4(uint32_t tq, uint32_t f, uint32_t
 // stand-alone kernel.  Restates gaussian_diffusion.py:341-349 (inpainting blend), :404-412
 // (x0-hat -> posterior mean), :569-585 / inpainting_gaussian_diffusion.py:51-63 (ancestral step)
 // and inpainting_gaussian_diffusion.py:157-177 (DDIM step) in the reference's operation order.
+// SAMPLER 2 is ddim_reverse_sample (gaussian_diffusion.py:910-946): the deterministic DDIM step run upward, x_t -> x_{t+1}.
 // ------------------------------------------------------------------------------------------
+// The fused kernels' MODE (0 model output only, 1 ancestral, 2 DDIM, 3 DDIM reverse) -> SAMPLER, and whether the step has a noise
+// term at all: MODE 3 has none, so its instantiations contain no Philox draw, no noise load and no noise mask -- a compile-time
+// property, not sigma = 0 times a draw.
+constexpr int step_sampler(int mode) { return mode == 3 ? 2 : mode == 2 ? 1 : 0; }
+constexpr bool step_draws(int mode) { return mode == 1 || mode == 2; }
 struct StepCoef {   // per-clip scalars gathered from the float32 tables at index t
     float c1, c2, sigma_ddpm;      // posterior_mean_coef1/2, nonzero * exp(0.5 * logvar)
     float srac, srm1ac;            // sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod
     float sq_abp, dir, sigma_ddim; // sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), nonzero * sigma
+                                   // (reverse step: sqrt(abar_next), sqrt(1 - abar_next), unused)
 };
 
 __device__ __forceinline__ StepCoef step_coef(const float* __restrict__ tab, int nsteps, int t, float eta) {
@@ -323,6 +330,27 @@ __device__ __forceinline__ StepCoef step_coef(const float* __restrict__ tab, int
     return c;
 }
 
+// The reverse step's scalars (:934-944).  alphas_cumprod_next[t] (:193, np.append(alphas_cumprod[1:], 0.0)) is row TAB_AC at t + 1 and
+// exactly 0 at the last index: no table row of its own (for a respaced schedule the table already is the respaced process's).
+__device__ __forceinline__ StepCoef step_coef_reverse(const float* __restrict__ tab, int nsteps, int t) {
+    StepCoef c;
+    c.c1 = tab[TAB_COEF1 * nsteps + t];            // (MEAN 2 only: x_prev -> x0-hat)
+    c.c2 = tab[TAB_COEF2 * nsteps + t];
+    c.sigma_ddpm = 0.0f;
+    c.srac = tab[TAB_SQRT_RECIP_AC * nsteps + t];
+    c.srm1ac = tab[TAB_SQRT_RECIPM1_AC * nsteps + t];
+    const float acn = t + 1 < nsteps ? tab[TAB_AC * nsteps + t + 1] : 0.0f;
+    c.sq_abp = sqrtf(acn);
+    c.dir = sqrtf(1.0f - acn);
+    c.sigma_ddim = 0.0f;
+    return c;
+}
+template <int SAMPLER>
+__device__ __forceinline__ StepCoef step_coef_for(const float* __restrict__ tab, int nsteps, int t, float eta) {
+    if constexpr (SAMPLER == 2) return step_coef_reverse(tab, nsteps, t);
+    else return step_coef(tab, nsteps, t, eta);
+}
+
 // returns the next sample; x0-hat (after blend / clip) is written to *pred.
 // MEAN: what the model predicts (reference :398-412, in the reference's order: the inpainting blend acts on the RAW model output, :341-349,
 // the conversion to x0-hat follows): 0 = x_start (every model the factories build, utils/model_util.py:172), 1 = epsilon
@@ -339,6 +367,10 @@ __device__ __forceinline__ float step_update(const StepCoef& c, float model_out,
     if (MEAN == 2) out = (1.0f / c.c1) * out - (c.c2 / c.c1) * x;
     if (clip) out = fminf(fmaxf(out, -1.0f), 1.0f);
     *pred = out;
+    if (SAMPLER == 2) {                                  // no noise term: `noise`, `mask_noise` are not read
+        float eps = (c.srac * x - out) / c.srm1ac;
+        return out * c.sq_abp + c.dir * eps;             // pred * sqrt(abar_next) + sqrt(1 - abar_next) * eps
+    }
     if (mask_noise) noise = noise * (1.0f - mask);
     if (SAMPLER == 0) {
         float mean = MEAN == 2 ? raw : c.c1 * out + c.c2 * x;
@@ -355,7 +387,10 @@ __device__ __forceinline__ float step_update(const StepCoef& c, float model_out,
 // seed) and every replay (the step counter `jbase` is advanced on the device at the end of each replay).
 struct LoopDev {
     float* x; const float* mask; const float* motion; const float* noise; const float* scale; float* xstart;
-    unsigned long long seed; float eta; int t_start; int nrun; int jbase; int pad;
+    unsigned long long seed; float eta; int t_start; int nrun; int jbase;
+    int up;                        // direction: 0 = step j visits index t_start - j (p_sample / ddim_sample), 1 = t_start + j (ddim_reverse_sample).
+                                   // Read by the kernels that do not know the sampler (the pose embedding's conditioning token, CondTok); a
+                                   // step kernel knows it from its MODE at compile time (step_resolve<UP>), so the descending ones are unchanged
 };
 
 // arguments of the fused diffusion step (output-projection epilogue)
@@ -370,7 +405,7 @@ struct StepArgs {
     unsigned long long seed; unsigned step; unsigned clip0;   // clip0: batch index of the slice's first clip (Philox counter)
     int mask_noise, clip, philox;
     // loop mode: the pointer fields above are PRESENCE flags (null / non-null) and are resolved in the kernel from *ld:
-    // step j = ld->jbase + joff visits index t_start - j; tensors start `eo` elements into the caller's, per-step buffers
+    // step j = ld->jbase + joff visits index t_start - j (t_start + j when ld->up); tensors start `eo` elements into the caller's, per-step buffers
     // (noise, x0-hat dump) advance by `step_stride` elements per step; the slice's scales start at clip `clip0`.
     const LoopDev* ld; int joff; unsigned long long eo, step_stride;
     // per (clip, feature) row of the inpainting mask: 0 = all zeros, 1 = all ones, 2 = mixed (k_mask_rowflags, once per loop).
@@ -379,11 +414,12 @@ struct StepArgs {
     const unsigned char* rowflag;
 };
 
+template <int UP = 0>
 __device__ __forceinline__ StepArgs step_resolve(StepArgs sa) {
     if (!sa.ld) return sa;
     const LoopDev d = *sa.ld;
     const int j = d.jbase + sa.joff;
-    sa.t = d.t_start - j;
+    sa.t = UP ? d.t_start + j : d.t_start - j;
     sa.eta = d.eta;
     sa.seed = d.seed;
     sa.step = (unsigned)j;

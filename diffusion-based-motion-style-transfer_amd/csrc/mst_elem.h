@@ -189,7 +189,7 @@ __global__ void k_q_sample(const float* __restrict__ tab, int nsteps, const floa
     }
 }
 
-// K10 / K10' stand-alone (model output produced elsewhere)
+// K10 / K10' stand-alone (model output produced elsewhere).  SAMPLER 2 (the reverse step) never reads `noise`: it may be null.
 template <int SAMPLER, int MEAN = 0>
 __global__ void k_step_epilogue(const float* __restrict__ tab, int nsteps, float eta,
                                 const float* __restrict__ model_out, const float* __restrict__ x,
@@ -198,7 +198,7 @@ __global__ void k_step_epilogue(const float* __restrict__ tab, int nsteps, float
                                 long long per_clip, int mask_noise, int clip_denoised,
                                 float* __restrict__ sample, float* __restrict__ xstart) {
     const int clip = blockIdx.y;
-    const StepCoef sc = step_coef(tab, nsteps, (int)t[clip], eta);
+    const StepCoef sc = step_coef_for<SAMPLER>(tab, nsteps, (int)t[clip], eta);
     const bool blend = mask != nullptr && motion != nullptr;
     const size_t base = (size_t)clip * per_clip;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < per_clip; i += (long long)gridDim.x * blockDim.x) {
@@ -206,7 +206,7 @@ __global__ void k_step_epilogue(const float* __restrict__ tab, int nsteps, float
         float m = mask ? mask[idx] : 0.f;
         float mot = blend ? motion[idx] : 0.f;
         float pred;
-        float nx = step_update<SAMPLER, MEAN>(sc, model_out[idx], x[idx], noise ? noise[idx] : 0.f, blend, m, mot,
+        float nx = step_update<SAMPLER, MEAN>(sc, model_out[idx], x[idx], (SAMPLER != 2 && noise) ? noise[idx] : 0.f, blend, m, mot,
                                               mask_noise && mask, clip_denoised, &pred);
         if (sample) sample[idx] = nx;
         if (xstart) xstart[idx] = pred;

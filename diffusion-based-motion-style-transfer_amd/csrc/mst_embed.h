@@ -93,6 +93,7 @@ __device__ __forceinline__ void emb_stream(const char* wsrc, unsigned w_voff, Be
 // load() -- x_t, bias and the mask row flags of ALL items issued at once (one memory latency; DEpiEmbedOut::finish takes three passes
 // of dependent loads); apply() -- the update itself (step_update, the same function as everywhere), stores, the next step's frame rows.
 // NU items per thread: item u = thread + 512 u, feature it / 16, frame group it % 16.
+// MODE 3 (the reverse step) has no noise term: noise1() is never called, load() reads no noise buffer, `nz` is never touched.
 template <int MODE, int NU>
 struct OutItems {
     f32x4 nz[NU], xv[NU], mk1, mot1;          // (mk1, mot1): mask / motion of the thread's FIRST item that needs them, prefetched (item u1)
@@ -130,7 +131,7 @@ struct OutItems {
     // every item's x_t, bias, row flag (and injected noise), issued back to back without a branch: an item beyond the thread's last one
     // re-reads that one (its values are never used)
     __device__ __forceinline__ void load(const DEpiEmbedOut<MODE>& epi, const StepArgs& sa) {
-        const bool use_noise = !sa.philox && sa.noise != nullptr;
+        const bool use_noise = step_draws(MODE) && !sa.philox && sa.noise != nullptr;
         const int ulast = nvalid > 0 ? nvalid - 1 : 0;
 #pragma unroll
         for (int u = 0; u < NU; u++) {
@@ -160,7 +161,7 @@ struct OutItems {
     }
     __device__ __forceinline__ void apply(const DEpiEmbedOut<MODE>& epi, const StepArgs& sa, float* tile) {
         constexpr int LDT = EmbCfg::BT + 4, TG = EmbCfg::BT / 4;
-        const StepCoef sc = step_coef(sa.tab, sa.nsteps, sa.t, sa.eta);
+        const StepCoef sc = step_coef_for<step_sampler(MODE)>(sa.tab, sa.nsteps, sa.t, sa.eta);
         const bool blend = sa.mask != nullptr && sa.motion != nullptr, use_mask = sa.mask != nullptr;
         float* trow = tile + f0 * LDT + (threadIdx.x % TG) * 4;
 #pragma unroll
@@ -183,14 +184,14 @@ struct OutItems {
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     float p;
-                    nx[j] = step_update<MODE == 2 ? 1 : 0>(sc, acc4[j] + bu[u], xv[u][j], nz[u][j], false, 0.f, 0.f, false, sa.clip, &p);
+                    nx[j] = step_update<step_sampler(MODE)>(sc, acc4[j] + bu[u], xv[u][j], step_draws(MODE) ? nz[u][j] : 0.f, false, 0.f, 0.f, false, sa.clip, &p);
                     pred[j] = p;
                 }
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     float p;
-                    nx[j] = step_update<MODE == 2 ? 1 : 0>(sc, acc4[j] + bu[u], xv[u][j], nz[u][j], blend, mk[j], mot[j], sa.mask_noise && use_mask, sa.clip, &p);
+                    nx[j] = step_update<step_sampler(MODE)>(sc, acc4[j] + bu[u], xv[u][j], step_draws(MODE) ? nz[u][j] : 0.f, blend, mk[j], mot[j], sa.mask_noise && use_mask, sa.clip, &p);
                     pred[j] = p;
                 }
             }
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(512) void k_embed_out(RowsFrames xs, const f16* __r
     const int tok0 = blockIdx.x * C::BT;
     const unsigned smem_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
     EMB_MARK(0)
-    const StepArgs sa = step_resolve(epi.sa);
+    const StepArgs sa = step_resolve<MODE == 3>(epi.sa);
     const char* wsrc = reinterpret_cast<const char*>(wpk) + (size_t)wave * NFR * 1024;
     const unsigned w_voff = (unsigned)lane * 16u;
     f32x4 acc[NX][NBW][4];
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(512) void k_embed_out(RowsFrames xs, const f16* __r
                 }
                 if constexpr (j % NBW == 0 && j / NBW + 1 < KS) xread(j / NBW + 1, (j / NBW + 1) & 1);      // one k-step ahead
                 // the noise of item k32, drawn in k-step k32: VALU work beside the MFMAs of a loop that mostly waits for its weight stream
-                if constexpr (MODE != 0 && EARLY_NOISE && j % NBW == 0 && j / NBW < NU) { if (staged) items.noise1(sa, j / NBW); }
+                if constexpr (step_draws(MODE) && EARLY_NOISE && j % NBW == 0 && j / NBW < NU) { if (staged) items.noise1(sa, j / NBW); }
             },
             [&](auto jc, f16x8 wf) {
                 constexpr int j = decltype(jc)::value;
@@ -321,8 +322,10 @@ __global__ __launch_bounds__(512) void k_embed_out(RowsFrames xs, const f16* __r
     if constexpr (MODE != 0) {
         if (staged) {
             if constexpr (!EARLY_NOISE) {                              // two accumulator sets: only now are registers free
+                if constexpr (step_draws(MODE)) {
 #pragma unroll
-                for (int u = 0; u < NU; u++) items.noise1(sa, u);
+                    for (int u = 0; u < NU; u++) items.noise1(sa, u);
+                }
                 items.load(epi, sa);
                 items.load_masked(sa);
             }
@@ -390,7 +393,7 @@ __global__ __launch_bounds__(512) void k_embed_out(RowsFrames xs, const f16* __r
                     for (int bi = 0; bi < 4; bi++) *reinterpret_cast<f32x4*>(trow + (16 * (wave + 8 * bi) + 4 * q4) * 4) = acc2[bi][tb];
                 }
                 __syncthreads();
-                epi_in.template finish<C::BT>(tok0, smem);
+                epi_in.template finish<C::BT>(tok0, smem, MODE == 3 ? 1 : 0);     // (the direction is this kernel's MODE: CondTok)
                 EMB_MARK(6)
                 return;
             }

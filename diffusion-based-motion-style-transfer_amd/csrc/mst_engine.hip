@@ -1833,19 +1833,21 @@ static int enqueue_step(mst_engine* e, const LoopPlan& p, int joff, int nsj, boo
         const float* const yes = reinterpret_cast<const float*>(1);
         sa.mask = a->inpainting_mask_dev ? yes : nullptr;
         sa.motion = a->inpainted_motion_dev ? yes : nullptr;
-        sa.noise = a->noise_mode == MST_NOISE_BUFFER ? yes : nullptr;
+        const bool draws = a->sampler != MST_SAMPLER_DDIM_REVERSE;      // the reverse step has no noise term: noise_mode, seed, noise_dev, mask_noise are not read
+        sa.noise = draws && a->noise_mode == MST_NOISE_BUFFER ? yes : nullptr;
         sa.scale = a->scale_dev ? yes : nullptr;
         sa.xstart = a->xstart_dump_dev ? reinterpret_cast<float*>(1) : nullptr;
         sa.clip0 = (unsigned)c0;
-        sa.mask_noise = a->mask_noise;
+        sa.mask_noise = draws ? a->mask_noise : 0;
         sa.clip = a->clip_denoised;
-        sa.philox = a->noise_mode == MST_NOISE_PHILOX;
+        sa.philox = draws && a->noise_mode == MST_NOISE_PHILOX;
         sa.ld = e->ld_dev;
         sa.joff = joff;
         sa.eo = eo;
         sa.step_stride = p.clip_elems;
         sa.rowflag = (a->inpainting_mask_dev && a->inpainted_motion_dev) ? e->rowflag + (size_t)c0 * e->cfg.feats : nullptr;
         if (a->sampler == MST_SAMPLER_DDPM) CHECK(launch_out_nt<1>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
+        else if (a->sampler == MST_SAMPLER_DDIM_REVERSE) CHECK(launch_out_nt<3>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
         else CHECK(launch_out_nt<2>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
     }
     return 0;
@@ -1870,11 +1872,18 @@ static int join_slices(mst_engine* e, const LoopPlan& p) {
 extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, void* stream) {
     if (!s || !a) return fail("mst_sample_loop: null argument");
     CHECK(check_ready(e, a->batch, a->frames, a->cfg));
-    if (a->t_start >= s->n || a->t_end < 0 || a->t_start < a->t_end)
+    if (a->sampler != MST_SAMPLER_DDPM && a->sampler != MST_SAMPLER_DDIM && a->sampler != MST_SAMPLER_DDIM_REVERSE)
+        return fail("mst_sample_loop: bad sampler %d", a->sampler);
+    const bool up = a->sampler == MST_SAMPLER_DDIM_REVERSE;      // ddim_reverse_sample: ascending indices, no noise term
+    if (up) {
+        if (a->t_start < 0 || a->t_end >= s->n || a->t_start > a->t_end)
+            return fail("mst_sample_loop: bad index range %d..%d for %d steps: the reverse sampler runs upward, 0 <= t_start <= t_end <= %d",
+                        a->t_start, a->t_end, s->n, s->n - 1);
+        if (a->eta != 0.0f) return fail("mst_sample_loop: Reverse ODE only for deterministic path (eta %g must be 0)", (double)a->eta);
+    } else if (a->t_start >= s->n || a->t_end < 0 || a->t_start < a->t_end)
         return fail("mst_sample_loop: bad index range %d..%d for %d steps", a->t_start, a->t_end, s->n);
     if (!a->x_dev || (a->cfg && !a->scale_dev)) return fail("mst_sample_loop: null x / scale");
-    if (a->noise_mode == MST_NOISE_BUFFER && !a->noise_dev) return fail("mst_sample_loop: noise buffer missing");
-    if (a->sampler != MST_SAMPLER_DDPM && a->sampler != MST_SAMPLER_DDIM) return fail("mst_sample_loop: bad sampler");
+    if (!up && a->noise_mode == MST_NOISE_BUFFER && !a->noise_dev) return fail("mst_sample_loop: noise buffer missing");
     if (styles_on(e)) CHECK(style_check(e, a->batch, a->frames));
     hipStream_t caller = (hipStream_t)stream;
     ON_DEVICE(e->cfg.device);
@@ -1884,11 +1893,12 @@ extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_l
     hipStream_t st = e->loop_stream;
     HIPCHECK(hipEventRecord(e->ev_in, caller));
     HIPCHECK(hipStreamWaitEvent(st, e->ev_in, 0));
-    const int nrun = a->t_start - a->t_end + 1;
-    // K1 hoisted: the timestep MLP for every index this loop visits (row j <-> index t_end + j)
+    const int nrun = (up ? a->t_end - a->t_start : a->t_start - a->t_end) + 1;
+    // K1 hoisted: the timestep MLP for every index this loop visits (row r <-> index min(t_start, t_end) + r: a descending loop's step j
+    // reads row nrun - 1 - j, an ascending one row j -- CondTok)
     e->prof_now = 0;
     CHECK(ensure_packed(e, st));
-    CHECK(timestep_rows(e, s->tmap + a->t_end, nrun, st));
+    CHECK(timestep_rows(e, s->tmap + (up ? a->t_start : a->t_end), nrun, st));
     // Clips are independent, so the batch runs as `nsplit` slices on separate streams: one slice's kernels fill
     // the CUs the other leaves idle in its prologues, tails and launch gaps (per-launch time is per-CU bound and
     // flat in the block count at this size).  CFG batches are sliced the same way (cond + uncond twins stay together).
@@ -1902,7 +1912,7 @@ extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_l
         HIPCHECK(hipEventSynchronize(e->ld_ev[slot]));
         LoopDev& h = e->ld_pin[slot];
         h = LoopDev{a->x_dev, a->inpainting_mask_dev, a->inpainted_motion_dev, a->noise_dev, a->scale_dev, a->xstart_dump_dev,
-                    a->seed, a->eta, a->t_start, nrun, 0, 0};
+                    a->seed, a->eta, a->t_start, nrun, 0, up ? 1 : 0};
         HIPCHECK(hipMemcpyAsync(e->ld_dev, &h, sizeof(LoopDev), hipMemcpyHostToDevice, st));
         HIPCHECK(hipEventRecord(e->ld_ev[slot], st));
     }
@@ -2012,7 +2022,10 @@ extern "C" int mst_step_epilogue_mt(const mst_schedule* s, const float* model_ou
                                     int32_t sampler, int32_t mean_type, float eta, int32_t mask_noise, int32_t clip_denoised, float* sample,
                                     float* xstart, void* stream) {
     if (!s || !model_out || !x || !t || batch < 1 || per_clip < 1) return fail("mst_step_epilogue: bad arguments");
-    if (sampler != MST_SAMPLER_DDPM && sampler != MST_SAMPLER_DDIM) return fail("mst_step_epilogue: bad sampler %d", sampler);
+    if (sampler != MST_SAMPLER_DDPM && sampler != MST_SAMPLER_DDIM && sampler != MST_SAMPLER_DDIM_REVERSE)
+        return fail("mst_step_epilogue: bad sampler %d", sampler);
+    if (sampler == MST_SAMPLER_DDIM_REVERSE && eta != 0.0f)
+        return fail("mst_step_epilogue: Reverse ODE only for deterministic path (eta %g must be 0)", (double)eta);
     if (mean_type < 0 || mean_type > 2) return fail("mst_step_epilogue: bad mean type %d (0 = x_start, 1 = epsilon, 2 = previous x)", mean_type);
     ON_DEVICE(s->device);
     int gx = (int)((per_clip + 255) / 256);
@@ -2020,11 +2033,11 @@ extern "C" int mst_step_epilogue_mt(const mst_schedule* s, const float* model_ou
 #define STEP_LAUNCH(S_, M_)                                                                                                              \
     hipLaunchKernelGGL((k_step_epilogue<S_, M_>), dim3(gx, batch), dim3(256), 0, (hipStream_t)stream, s->tab, s->n, eta, model_out, x,   \
                        noise, mask, motion, (const long long*)t, (long long)per_clip, mask_noise, clip_denoised, sample, xstart)
-    const bool ddim = sampler == MST_SAMPLER_DDIM;
+    const bool ddim = sampler == MST_SAMPLER_DDIM, rev = sampler == MST_SAMPLER_DDIM_REVERSE;      // (rev: `noise` is never read, may be null)
     switch (mean_type) {
-        case 0: if (ddim) STEP_LAUNCH(1, 0); else STEP_LAUNCH(0, 0); break;
-        case 1: if (ddim) STEP_LAUNCH(1, 1); else STEP_LAUNCH(0, 1); break;
-        default: if (ddim) STEP_LAUNCH(1, 2); else STEP_LAUNCH(0, 2); break;
+        case 0: if (rev) STEP_LAUNCH(2, 0); else if (ddim) STEP_LAUNCH(1, 0); else STEP_LAUNCH(0, 0); break;
+        case 1: if (rev) STEP_LAUNCH(2, 1); else if (ddim) STEP_LAUNCH(1, 1); else STEP_LAUNCH(0, 1); break;
+        default: if (rev) STEP_LAUNCH(2, 2); else if (ddim) STEP_LAUNCH(1, 2); else STEP_LAUNCH(0, 2); break;
     }
 #undef STEP_LAUNCH
     HIPCHECK(hipGetLastError());
@@ -2052,6 +2065,8 @@ extern "C" int mst_step_backward(const mst_schedule* s, const float* g_sample, c
     else if (sampler == MST_SAMPLER_DDIM)
         hipLaunchKernelGGL(k_step_backward<1>, dim3(gx, batch), dim3(256), 0, (hipStream_t)stream, s->tab, s->n, eta, g_sample, g_pred, mask,
                            has_blend, (const long long*)t, (long long)per_clip, pred_clipped, d_model_out);
+    else if (sampler == MST_SAMPLER_DDIM_REVERSE)
+        return fail("mst_step_backward: MST_SAMPLER_DDIM_REVERSE has no backward: the reference has no _with_grad form of ddim_reverse_sample");
     else
         return fail("mst_step_backward: bad sampler %d", sampler);
     HIPCHECK(hipGetLastError());

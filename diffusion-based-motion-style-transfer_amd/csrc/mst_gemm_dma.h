@@ -502,8 +502,10 @@ struct DEpiEmbedIn {
     }
     // everything behind the accumulator -> LDS rows hop (smem: BT rows of LD = 2064 bytes, fp32): + bias + positional row -> the stream's
     // hi / lo rows, whole-row stores; conditioning tokens.  Shared by the ring GEMM above and k_embed_in (mst_embed.h).
+    // dir: the sampling loop's direction where the caller knows it at compile time (a step kernel that embeds the next step: 0 down,
+    // 1 up), -1 = read it from the loop block (LoopDev::up)
     template <int BT>
-    __device__ __forceinline__ void finish(int tok0, char* smem) const {
+    __device__ __forceinline__ void finish(int tok0, char* smem, int dir = -1) const {
         constexpr int LD = MST_D * 4 + 16;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         const int fa = lane * 4, fb = 256 + lane * 4;
@@ -557,7 +559,13 @@ struct DEpiEmbedIn {
             static_assert(MST_D == 512, "one thread per feature");
             const int f = threadIdx.x, x_clips = total / T;
             int uniform_row = ct.uniform_row;
-            if (ct.ld) uniform_row = ct.ld->nrun - 1 - (ct.ld->jbase + ct.joff);      // sampling loop: the timestep row of step jbase + joff
+            // sampling loop: the timestep row of step j = jbase + joff.  The table's row r is index min(t_start, t_end) + r
+            // (mst_sample_loop), so a descending loop reads row nrun - 1 - j and an ascending one row j.
+            if (ct.ld) {
+                const int j = ct.ld->jbase + ct.joff;
+                const bool up = dir >= 0 ? dir != 0 : ct.ld->up != 0;
+                uniform_row = up ? j : ct.ld->nrun - 1 - j;
+            }
             const int lim = tok0 + BT < total ? tok0 + BT : total;
             for (int c = (tok0 + T - 1) / T; c * T < lim; c++)
                 for (int clip = c; clip < ct.rows; clip += x_clips) {                // the clip and, under CFG, its uncond twin
@@ -580,7 +588,8 @@ struct DEpiEmbedIn {
 // frames) items with float4 accesses to x_t / mask / motion / noise / outputs -- the [clip][feature][frame]
 // tensors are frame-contiguous, so a wave touches 256-B runs.  (First version: per-lane scalar gathers
 // straight from the accumulator layout, all work in 4-5 of the 8 waves: 36 us even at batch 16.)
-// MODE 0 model output only, 1 ancestral step, 2 DDIM step; NX = 2 is the CFG doubled batch.
+// MODE 0 model output only, 1 ancestral step, 2 DDIM step, 3 DDIM reverse step (x_t -> x_{t+1}: no noise term, so no draw, no noise
+// load and no noise mask in its instantiations); NX = 2 is the CFG doubled batch.
 template <int MODE>
 struct DEpiEmbedOut {
     const float* bias; int F, T, total; float* out; StepArgs sa;
@@ -594,7 +603,7 @@ struct DEpiEmbedOut {
         if (MODE == 0) { out[idx] = mo; return; }
         const float mk = use_mask ? sa.mask[idx] : 0.f, mot = blend ? sa.motion[idx] : 0.f;
         float pred;
-        const float nx = step_update<MODE == 2 ? 1 : 0>(sc, mo, sa.x[idx], nz, blend, mk, mot, sa.mask_noise && use_mask, sa.clip, &pred);
+        const float nx = step_update<step_sampler(MODE)>(sc, mo, sa.x[idx], nz, blend, mk, mot, sa.mask_noise && use_mask, sa.clip, &pred);
         sa.sample[idx] = nx;
         if (sa.xstart) sa.xstart[idx] = pred;
     }
@@ -603,7 +612,7 @@ struct DEpiEmbedOut {
     __device__ __forceinline__ void run(f32x16 (&acc)[NX][MT][NT], int tok0, int f0, char* smem) const {
         constexpr int LDT = BT + 4;                          // floats per feature row of the tile
         DLane<BT, BF, MT, NT> lc;
-        const StepArgs sa = step_resolve(this->sa);          // loop mode: tensors and step index come from device memory
+        const StepArgs sa = step_resolve<MODE == 3>(this->sa);          // loop mode: tensors and step index come from device memory
         float* tile = reinterpret_cast<float*>(smem);
 #pragma unroll
         for (int m = 0; m < MT; m++) {
@@ -630,9 +639,10 @@ struct DEpiEmbedOut {
         constexpr int LDT = BT + 4;
         float* tile = reinterpret_cast<float*>(smem);
         StepCoef sc;
-        if (MODE != 0) sc = step_coef(sa.tab, sa.nsteps, sa.t, sa.eta);
+        if (MODE != 0) sc = step_coef_for<step_sampler(MODE)>(sa.tab, sa.nsteps, sa.t, sa.eta);
         const bool blend = sa.mask != nullptr && sa.motion != nullptr, use_mask = sa.mask != nullptr;
-        const bool use_noise = !sa.philox && sa.noise != nullptr;
+        const bool use_noise = step_draws(MODE) && !sa.philox && sa.noise != nullptr;
+        const bool philox = step_draws(MODE) && sa.philox;
         const bool vec = (T & 3) == 0;                       // 4 consecutive frames never straddle a clip
         constexpr int TG = BT / 4;
         if (vec && MODE != 0) {
@@ -681,7 +691,7 @@ struct DEpiEmbedOut {
                     f32x4 mo;
 #pragma unroll
                     for (int j = 0; j < 4; j++) mo[j] = acc4[j] + bu[u];
-                    if (sa.philox) {
+                    if (philox) {
                         float nrm[4];
                         philox_normal4((unsigned)(tu[u] >> 2), (unsigned)fu[u], (unsigned)clipu[u] + sa.clip0, sa.step, sa.seed, nrm);
 #pragma unroll
@@ -691,7 +701,7 @@ struct DEpiEmbedOut {
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         float p;
-                        nx[j] = step_update<MODE == 2 ? 1 : 0>(sc, mo[j], xv[u][j], nz[u][j], blend, mk[u][j], mot[u][j], sa.mask_noise && use_mask, sa.clip, &p);
+                        nx[j] = step_update<step_sampler(MODE)>(sc, mo[j], xv[u][j], nz[u][j], blend, mk[u][j], mot[u][j], sa.mask_noise && use_mask, sa.clip, &p);
                         pred[j] = p;
                     }
                     *reinterpret_cast<f32x4*>(sa.sample + idx[u]) = nx;
@@ -721,7 +731,7 @@ struct DEpiEmbedOut {
                     const int clip = tk / T, t = tk - clip * T;
                     const size_t idx = ((size_t)clip * F + f) * T + t;
                     float nz = use_noise ? sa.noise[idx] : 0.f;
-                    if (MODE != 0 && sa.philox) {
+                    if (MODE != 0 && philox) {
                         float nrm[4];
                         philox_normal4((unsigned)(t >> 2), (unsigned)f, (unsigned)clip + sa.clip0, sa.step, sa.seed, nrm);
                         nz = nrm[t & 3];

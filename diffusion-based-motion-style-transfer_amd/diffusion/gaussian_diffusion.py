@@ -2,7 +2,7 @@
 
 Same public names, signatures and numpy float64 tables as the reference (GaussianDiffusion
 :111-221, q_sample :267-285, p_mean_variance :311-424, p_sample :532-585, p_sample_loop(_progressive)
-:644-794, ddim_sample :796-860, ddim_sample_loop(_progressive) :948-1082, masked_l2 :223-235,
+:644-794, ddim_sample :796-860, ddim_reverse_sample :910-946, ddim_sample_loop(_progressive) :948-1082, masked_l2 :223-235,
 _extract_into_tensor :1605-1618, schedules :22-66), but the arithmetic runs in the HIP library:
 
   * model is an engine-backed denoiser (mst_amd.model.StyleDiffusion / MDM, optionally wrapped in
@@ -290,9 +290,11 @@ class GaussianDiffusion:
             raise NotImplementedError("cond_fn / denoised_fn are never set by this code base (SURVEY.md section 9)")
         with th.no_grad():
             out = self._model_output(model, x, t, model_kwargs)
-        noise = self._draw(x, const_noise)
+        # (the reverse step has no noise term: nothing is drawn, so the caller's generator is left where it was)
+        reverse = sampler == _eng.SAMPLER_DDIM_REVERSE
+        noise = None if reverse else self._draw(x, const_noise)
         mask, motion = self._inpaint_pair(model_kwargs)
-        nmask = self._noise_mask(model_kwargs)
+        nmask = None if reverse else self._noise_mask(model_kwargs)      # (no noise, no noise mask: y needs no 'inpainting_mask', :910-946)
         # epsilon / previous-x models: converted to x0-hat INSIDE the step kernel (MODEs of k_step_epilogue), behind the inpainting blend
         # as the reference orders them (:341-349 then :398-412)
         mean_type = {ModelMeanType.START_X: 0, ModelMeanType.EPSILON: 1, ModelMeanType.PREVIOUS_X: 2}[self.model_mean_type]
@@ -308,6 +310,12 @@ class GaussianDiffusion:
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                     eta=0.0, pred_xstart_in_graph=False):
         return self._fused_step(_eng.SAMPLER_DDIM, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, False, eta)
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+        """x_t -> x_{t+1} by the DDIM reverse ODE (reference :910-946), the deterministic step run upward: DDIM inversion.
+        `alphas_cumprod_next[t]` is read inside the step kernel as alphas_cumprod[t + 1], and 0 at the last index."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        return self._fused_step(_eng.SAMPLER_DDIM_REVERSE, model, x, t, clip_denoised, denoised_fn, None, model_kwargs, False, 0.0)
 
     # -- autograd-carrying variants (fine-tune loss): x0-hat may stay in the graph ---------------
     def _grad_step(self, ddim, model, x, t, clip_denoised, model_kwargs, pred_xstart_in_graph, const_noise=False, eta=0.0):
@@ -349,12 +357,17 @@ class GaussianDiffusion:
         return self._grad_step(True, model, x, t, clip_denoised, model_kwargs, pred_xstart_in_graph, False, eta)
 
     # ------------------------------------------------------------------------------ loops
-    def _loop_setup(self, model, shape, noise, device, skip_timesteps, init_image, stop_timesteps, model_kwargs):
+    @staticmethod
+    def _loop_device(model, device):
         if device is None:
             try:
                 device = next(model.parameters()).device
             except Exception:
                 device = next(model.model.parameters()).device
+        return device
+
+    def _loop_setup(self, model, shape, noise, device, skip_timesteps, init_image, stop_timesteps, model_kwargs):
+        device = self._loop_device(model, device)
         assert isinstance(shape, (tuple, list))
         img = noise if noise is not None else th.randn(*shape, device=device)
         if skip_timesteps and init_image is None:
@@ -377,12 +390,13 @@ class GaussianDiffusion:
         y = self._y(model_kwargs)
         eng = denoiser.mst_engine(img.shape[0] * (2 if cfg is not None else 1), img.shape[-1])
         denoiser.mst_prepare(eng, y, cfg is not None)
+        reverse = sampler == _eng.SAMPLER_DDIM_REVERSE      # no noise term: no buffer, no seed, no noise mask, no draw from torch's generator
         mask, motion = self._inpaint_pair(model_kwargs)
-        nmask = self._noise_mask(model_kwargs)
+        nmask = None if reverse else self._noise_mask(model_kwargs)
         scale = y['scale'] if cfg is not None else None
         sch = self._schedule(img.device)
         x = img.contiguous().float().clone()
-        philox = self.noise_source == "philox"
+        philox = self.noise_source == "philox" or reverse
         # const_noise (reference :569-572, `_draw`: every clip gets clip 0's noise): the in-kernel draw is keyed by the clip index, so
         # the philox source then draws ONE clip's numbers with the same generator (philox_normal, key seed + c0, step j) and hands them
         # to the loop as buffer noise repeated over the batch, in chunks bounded like the torch source's
@@ -394,7 +408,7 @@ class GaussianDiffusion:
             chunk = len(indices) if not want_xstart else max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
         else:
             chunk = max(1, min(int(self.noise_chunk), int(self.noise_chunk_bytes // (x.numel() * 4))))
-        seed = int(th.randint(0, 2 ** 31 - 1, (1,)).item()) if philox else 0
+        seed = int(th.randint(0, 2 ** 31 - 1, (1,)).item()) if philox and not reverse else 0
         if cfg is not None:
             eng.check_guidance_scale(scale)                 # once per loop (engine.CFG_SCALE_MAX), not per chunk or step
         it = range(0, len(indices), chunk)
@@ -443,8 +457,14 @@ class GaussianDiffusion:
                                         const_noise, pred_xstart_in_graph, chain)
             return
         device, img, indices = self._loop_setup(model, shape, noise, device, skip_timesteps, init_image, stop_timesteps, model_kwargs)
+        yield from self._steps_from(_eng.SAMPLER_DDIM if ddim else _eng.SAMPLER_DDPM, model, device, img, indices, clip_denoised,
+                                    denoised_fn, cond_fn, model_kwargs, const_noise, eta, progress, chunked, want_xstart)
+
+    def _steps_from(self, sampler, model, device, img, indices, clip_denoised, denoised_fn, cond_fn, model_kwargs, const_noise, eta,
+                    progress, chunked, want_xstart):
+        """The no-grad steps of every loop entry, from `img` as it is through `indices` in their order (descending for p_sample /
+        ddim_sample, ascending for ddim_reverse_sample): inside the library when the denoiser is native, step by step otherwise."""
         denoiser, cfg, _ = _unwrap(model)
-        sampler = _eng.SAMPLER_DDIM if ddim else _eng.SAMPLER_DDPM
         if (denoiser is not None and cond_fn is None and denoised_fn is None and not denoiser.training
                 and self.model_mean_type == ModelMeanType.START_X):
             yield from self._engine_loop(sampler, denoiser, cfg, img, indices, clip_denoised, model_kwargs, const_noise, eta,
@@ -456,10 +476,12 @@ class GaussianDiffusion:
         for i in indices:
             # (the reference's th.tensor([i] * B, device=...) at gaussian_diffusion.py:775 / :1063 is a blocking host-to-device copy: it would
             # drain the GPU once per chained step of the fine-tune objective; a device-side fill gives the same tensor)
-            t = th.full((shape[0],), int(i), device=device, dtype=th.long)
+            t = th.full((img.shape[0],), int(i), device=device, dtype=th.long)
             with th.no_grad():
-                out = (self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                        model_kwargs=model_kwargs, eta=eta) if ddim else
+                out = (self.ddim_reverse_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                                model_kwargs=model_kwargs, eta=eta) if sampler == _eng.SAMPLER_DDIM_REVERSE else
+                       self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                        model_kwargs=model_kwargs, eta=eta) if sampler == _eng.SAMPLER_DDIM else
                        self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
                                      model_kwargs=model_kwargs, const_noise=const_noise))
                 yield out
@@ -540,6 +562,49 @@ class GaussianDiffusion:
                 True, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, skip_timesteps,
                 init_image, randomize_class, cond_fn_with_grad, False, pred_xstart_in_graph, stop_timesteps, eta, chunked=True,
                 want_xstart=bool(dump_all_xstart)):
+            if dump_all_xstart:
+                dump.append(out["pred_xstart"])
+            final = out
+        return dump if dump_all_xstart else final["sample"]
+
+    # -- DDIM inversion and its decode half.  The reference has the step (ddim_reverse_sample) and no loop around it: these entries
+    #    are additions.
+    def _reverse_loop(self, model, x_start, num_steps, clip_denoised, model_kwargs, device, progress, chunked, want_xstart):
+        n = self.num_timesteps if num_steps is None else int(num_steps)
+        if not 1 <= n <= self.num_timesteps:
+            raise ValueError(f"ddim_reverse_sample_loop: num_steps {n} outside 1..{self.num_timesteps}")
+        device = self._loop_device(model, device)
+        yield from self._steps_from(_eng.SAMPLER_DDIM_REVERSE, model, device, x_start.to(device), list(range(n)), clip_denoised,
+                                    None, None, model_kwargs, False, 0.0, progress, chunked, want_xstart)
+
+    def ddim_reverse_sample_loop_progressive(self, model, x_start, num_steps=None, clip_denoised=True, model_kwargs=None,
+                                             device=None, progress=False):
+        """ddim_reverse_sample at indices 0 .. num_steps - 1 (default: the whole process), one dict per step: 'sample' is x at the
+        step's index + 1.  Deterministic: nothing is drawn."""
+        yield from self._reverse_loop(model, x_start, num_steps, clip_denoised, model_kwargs, device, progress, False, True)
+
+    def ddim_reverse_sample_loop(self, model, x_start, num_steps=None, clip_denoised=True, model_kwargs=None, device=None,
+                                 progress=False, dump_all_xstart=False):
+        """DDIM inversion: x at index num_steps of the deterministic process that starts at `x_start` (or every step's x0-hat)."""
+        dump, final = [], None
+        for out in self._reverse_loop(model, x_start, num_steps, clip_denoised, model_kwargs, device, progress, True,
+                                      bool(dump_all_xstart)):
+            if dump_all_xstart:
+                dump.append(out["pred_xstart"])
+            final = out
+        return dump if dump_all_xstart else final["sample"]
+
+    def ddim_sample_loop_from(self, model, x_t, num_steps, eta=0.0, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                              model_kwargs=None, device=None, progress=False, dump_all_xstart=False):
+        """ddim_sample at indices num_steps - 1 .. 0 starting from `x_t` AS IT IS: no q_sample, no initial draw -- the decode half
+        of a (partial) inversion.  With num_steps == num_timesteps this is ddim_sample_loop(noise=x_t)."""
+        n = int(num_steps)
+        if not 1 <= n <= self.num_timesteps:
+            raise ValueError(f"ddim_sample_loop_from: num_steps {n} outside 1..{self.num_timesteps}")
+        device = self._loop_device(model, device)
+        dump, final = [], None
+        for out in self._steps_from(_eng.SAMPLER_DDIM, model, device, x_t.to(device), list(range(n))[::-1], clip_denoised, denoised_fn,
+                                    cond_fn, model_kwargs, False, eta, progress, True, bool(dump_all_xstart)):
             if dump_all_xstart:
                 dump.append(out["pred_xstart"])
             final = out

@@ -11,6 +11,7 @@ import torch
 from . import _native as N
 
 SAMPLER_DDPM, SAMPLER_DDIM = 0, 1
+SAMPLER_DDIM_REVERSE = 2        # x_t -> x_{t+1}, the deterministic DDIM step run upward (gaussian_diffusion.py:910-946); no noise term
 NOISE_BUFFER, NOISE_PHILOX = 0, 1
 
 # Largest classifier-free guidance factor (the larger of s and 1 - s per clip) at which the default f16-operand path was measured to
@@ -91,8 +92,9 @@ class Schedule:
 
     def step(self, model_output, x, t, noise, sampler=SAMPLER_DDPM, eta=0.0, mask=None, motion=None,
              mask_noise=False, clip_denoised=False, mean_type=0):
-        """(sample, pred_xstart) of one p_sample / ddim_sample step given the model output.
-        mean_type: what the model predicts -- 0 x_start, 1 epsilon, 2 previous x (converted inside the kernel, reference :398-412)."""
+        """(sample, pred_xstart) of one p_sample / ddim_sample / ddim_reverse_sample step given the model output.
+        mean_type: what the model predicts -- 0 x_start, 1 epsilon, 2 previous x (converted inside the kernel, reference :398-412).
+        SAMPLER_DDIM_REVERSE draws nothing: `noise` may be None and is never read, `eta` must be 0."""
         dev = x.device
         mo = _f32c(model_output, dev, "model_output")
         x = _f32c(x, dev, "x")
@@ -411,14 +413,15 @@ class DenoiserEngine:
     def sample_loop(self, schedule, x, t_start, t_end=0, sampler=SAMPLER_DDPM, eta=0.0, cfg=False, scale=None,
                     mask=None, motion=None, mask_noise=True, clip_denoised=False, noise=None, seed=None,
                     dump_xstart=False):
-        """Run diffusion indices t_start..t_end in place on `x` ([B,F,1,T] float32 GPU tensor).
-        noise: [nsteps,B,F,1,T] tensor (injected draws) or None -> in-kernel Philox with `seed`.
-        Returns x (and the [nsteps,B,F,1,T] x0-hat dump when requested)."""
+        """Run diffusion indices t_start..t_end in place on `x` ([B,F,1,T] float32 GPU tensor): downward (t_start >= t_end) for
+        SAMPLER_DDPM / SAMPLER_DDIM, upward (t_start <= t_end; x leaves as x at index t_end + 1) for SAMPLER_DDIM_REVERSE.
+        noise: [nsteps,B,F,1,T] tensor (injected draws) or None -> in-kernel Philox with `seed`; the reverse sampler reads neither.
+        Returns x (and the [nsteps,B,F,1,T] x0-hat dump, entry j = executed step j, when requested)."""
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         if cfg:
             self.check_guidance_scale(scale)
         B, F, one, T = x.shape
-        nsteps = t_start - t_end + 1
+        nsteps = abs(t_start - t_end) + 1                  # (a range against the sampler's direction is refused by the library)
         a = N.MstLoopArgs()
         a.batch, a.frames, a.cfg, a.sampler = B, T, int(bool(cfg)), int(sampler)
         a.mask_noise, a.clip_denoised = int(bool(mask_noise)), int(bool(clip_denoised))

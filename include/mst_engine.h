@@ -140,7 +140,12 @@ int mst_forward(mst_engine* e, const float* x_dev, const int64_t* t_dev, const f
  * (inpainting_gaussian_diffusion.py:125-177) fused into the output-projection kernel.
  * Runs diffusion indices t_start, t_start-1, ..., t_end (t_start == t_end: one step).
  * ----------------------------------------------------------------------------------------- */
-enum { MST_SAMPLER_DDPM = 0, MST_SAMPLER_DDIM = 1 };
+/* MST_SAMPLER_DDIM_REVERSE: ddim_reverse_sample (gaussian_diffusion.py:910-946), x_t -> x_{t+1}, the deterministic DDIM step run
+ * upward (DDIM inversion).  Its index range is inclusive and ASCENDING, 0 <= t_start <= t_end <= n - 1: the loop visits t_start,
+ * t_start + 1, ..., t_end and leaves x at index t_end + 1.  eta must be 0 ("Reverse ODE only for deterministic path", :923).  The
+ * step has no noise term: noise_mode, seed and mask_noise are ignored and noise_dev may be NULL.  alphas_cumprod_next[t] (:193) is
+ * read as MST_TAB alphas_cumprod[t + 1], and 0 at t == n - 1: the schedule's table layout is unchanged. */
+enum { MST_SAMPLER_DDPM = 0, MST_SAMPLER_DDIM = 1, MST_SAMPLER_DDIM_REVERSE = 2 };
 enum { MST_NOISE_BUFFER = 0, MST_NOISE_PHILOX = 1 };
 
 typedef struct mst_loop_args {
@@ -151,7 +156,7 @@ typedef struct mst_loop_args {
     int32_t mask_noise;             /* 1: InpaintingGaussianDiffusion (noise *= 1 - mask)        */
     int32_t clip_denoised;          /* clamp x0-hat to [-1, 1] (callers pass 0)                  */
     int32_t noise_mode;             /* MST_NOISE_*                                               */
-    int32_t t_start, t_end;         /* inclusive, t_start >= t_end >= 0                          */
+    int32_t t_start, t_end;         /* inclusive, t_start >= t_end >= 0 (DDIM_REVERSE: t_start <= t_end) */
     float   eta;                    /* DDIM eta                                                  */
     uint64_t seed;                  /* Philox key (MST_NOISE_PHILOX)                             */
     const float* scale_dev;         /* [B] guidance scale (cfg)                                  */
@@ -180,7 +185,9 @@ int mst_loop_slices(const mst_engine* e, int32_t batch, int32_t cfg, int32_t fra
  *                       diffusion/inpainting_gaussian_diffusion.py:6-23
  *   mst_step_epilogue   gaussian_diffusion.py:341-349 (blend), :387-412 (mean/variance),
  *                       :569-585 / inpainting_gaussian_diffusion.py:51-63 (p_sample),
- *                       inpainting_gaussian_diffusion.py:157-177 (ddim_sample)
+ *                       inpainting_gaussian_diffusion.py:157-177 (ddim_sample),
+ *                       gaussian_diffusion.py:910-946 (ddim_reverse_sample: sampler MST_SAMPLER_DDIM_REVERSE, eta 0,
+ *                       noise_dev never read and may be NULL)
  * t_dev is int64 [batch] of indices into the schedule.  sample_out_dev / xstart_out_dev may be NULL.
  * ----------------------------------------------------------------------------------------- */
 int mst_q_sample(const mst_schedule* s, const float* x_start_dev, const float* noise_dev,
@@ -212,6 +219,7 @@ int mst_step_epilogue_mt(const mst_schedule* s, const float* model_out_dev, cons
  * g_sample / g_pred: upstream gradients of the two outputs, either may be NULL (= zero).  has_blend: the forward blended
  * with (mask, motion).  pred_clipped_dev: NULL, or -- when the forward ran with clip_denoised (the reference signature's default,
  * gaussian_diffusion.py:389-395) -- its x0-hat output: the clamp's gradient mask (zero where the prediction saturated at +-1). */
+/* MST_SAMPLER_DDIM_REVERSE is refused: the reference has no `_with_grad` form of ddim_reverse_sample. */
 int mst_step_backward(const mst_schedule* s, const float* g_sample_dev, const float* g_pred_dev, const float* mask_dev,
                       int32_t has_blend, const int64_t* t_dev, int32_t batch, int64_t per_clip, int32_t sampler, float eta,
                       const float* pred_clipped_dev, float* d_model_out_dev, void* stream);
