@@ -30,6 +30,10 @@ class MstLoopArgs(C.Structure):
         ("xstart_dump_dev", C.c_void_p)]
 
 
+class MstPlmsArgs(C.Structure):
+    _fields_ = [("order", C.c_int32), ("steps_done", C.c_int32), ("hist_dev", C.c_void_p)]
+
+
 # name -> (restype, argtypes); must list every function include/mst_engine.h declares
 SIGNATURES = {
     "mst_last_error": (C.c_char_p, []),
@@ -47,6 +51,12 @@ SIGNATURES = {
     "mst_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_void_p]),
     "mst_sample_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.c_void_p]),
+    "mst_sample_loop_plms": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.POINTER(MstPlmsArgs), C.c_void_p]),
+    "mst_plms_epilogue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mst_plms_euler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mst_loop_slices": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "mst_q_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
                                C.c_void_p, C.c_void_p]),

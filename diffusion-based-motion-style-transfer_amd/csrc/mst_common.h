@@ -301,11 +301,12 @@ __device__ __forceinline__ void philox_normal4(uint32_t tq, uint32_t f, uint32_t
 // (x0-hat -> posterior mean), :569-585 / inpainting_gaussian_diffusion.py:51-63 (ancestral step)
 // and inpainting_gaussian_diffusion.py:157-177 (DDIM step) in the reference's operation order.
 // SAMPLER 2 is ddim_reverse_sample (gaussian_diffusion.py:910-946): the deterministic DDIM step run upward, x_t -> x_{t+1}.
+// SAMPLER 3 is the multistep step of plms_sample (gaussian_diffusion.py:1084-1166): its update is plms_update below, not step_update.
 // ------------------------------------------------------------------------------------------
-// The fused kernels' MODE (0 model output only, 1 ancestral, 2 DDIM, 3 DDIM reverse) -> SAMPLER, and whether the step has a noise
-// term at all: MODE 3 has none, so its instantiations contain no Philox draw, no noise load and no noise mask -- a compile-time
-// property, not sigma = 0 times a draw.
-constexpr int step_sampler(int mode) { return mode == 3 ? 2 : mode == 2 ? 1 : 0; }
+// The fused kernels' MODE (0 model output only, 1 ancestral, 2 DDIM, 3 DDIM reverse, 4 PLMS multistep) -> SAMPLER, and whether the step
+// has a noise term at all: MODEs 3 and 4 have none, so their instantiations contain no Philox draw, no noise load and no noise mask -- a
+// compile-time property, not sigma = 0 times a draw.
+constexpr int step_sampler(int mode) { return mode == 4 ? 3 : mode == 3 ? 2 : mode == 2 ? 1 : 0; }
 constexpr bool step_draws(int mode) { return mode == 1 || mode == 2; }
 struct StepCoef {   // per-clip scalars gathered from the float32 tables at index t
     float c1, c2, sigma_ddpm;      // posterior_mean_coef1/2, nonzero * exp(0.5 * logvar)
@@ -345,9 +346,24 @@ __device__ __forceinline__ StepCoef step_coef_reverse(const float* __restrict__ 
     c.sigma_ddim = 0.0f;
     return c;
 }
+// The PLMS step's scalars (:1130-1131, :1137-1158), all at index t: sqrt(abar_prev), sqrt(1 - abar_prev); no sigma.
+__device__ __forceinline__ StepCoef step_coef_plms(const float* __restrict__ tab, int nsteps, int t) {
+    StepCoef c;
+    c.c1 = tab[TAB_COEF1 * nsteps + t];            // (MEAN 2 only: x_prev -> x0-hat)
+    c.c2 = tab[TAB_COEF2 * nsteps + t];
+    c.sigma_ddpm = 0.0f;
+    c.srac = tab[TAB_SQRT_RECIP_AC * nsteps + t];
+    c.srm1ac = tab[TAB_SQRT_RECIPM1_AC * nsteps + t];
+    const float abp = tab[TAB_AC_PREV * nsteps + t];
+    c.sq_abp = sqrtf(abp);
+    c.dir = sqrtf(1.0f - abp);
+    c.sigma_ddim = 0.0f;
+    return c;
+}
 template <int SAMPLER>
 __device__ __forceinline__ StepCoef step_coef_for(const float* __restrict__ tab, int nsteps, int t, float eta) {
-    if constexpr (SAMPLER == 2) return step_coef_reverse(tab, nsteps, t);
+    if constexpr (SAMPLER == 3) return step_coef_plms(tab, nsteps, t);
+    else if constexpr (SAMPLER == 2) return step_coef_reverse(tab, nsteps, t);
     else return step_coef(tab, nsteps, t, eta);
 }
 
@@ -382,6 +398,54 @@ __device__ __forceinline__ float step_update(const StepCoef& c, float model_out,
     }
 }
 
+// The model output -> x0-hat of every sampler (blend on the RAW output, conversion, clip), as the first lines of step_update.
+template <int MEAN>
+__device__ __forceinline__ float step_pred(const StepCoef& c, float model_out, float x, bool has_blend, float mask, float motion, bool clip) {
+    float out = model_out;
+    if (has_blend) out = out * (1.0f - mask) + motion * mask;
+    if (MEAN == 1) out = c.srac * x - c.srm1ac * out;
+    if (MEAN == 2) out = (1.0f / c.c1) * out - (c.c2 / c.c1) * x;
+    if (clip) out = fminf(fmaxf(out, -1.0f), 1.0f);
+    return out;
+}
+// The Adams-Bashforth combination of plms_sample (:1147-1154): `eps` is this step's, e1 the newest earlier one, e3 the oldest.
+__device__ __forceinline__ float plms_eps_prime(int cur_order, float eps, float e1, float e2, float e3) {
+    if (cur_order == 2) return (3.0f * eps - e1) / 2.0f;
+    if (cur_order == 3) return (23.0f * eps - 16.0f * e1 + 5.0f * e2) / 12.0f;
+    if (cur_order == 4) return (55.0f * eps - 59.0f * e1 + 37.0f * e2 - 9.0f * e3) / 24.0f;
+    return eps;
+}
+// One element of plms_sample (gaussian_diffusion.py:1084-1166) in the reference's operation order; every site of the diffusion update
+// calls it for the PLMS step.  cur_order 1..4: the multistep step -- eps' from the history, pred' = srac x - srm1ac eps' (NOT
+// clipped), mean = pred' sqrt(abar_prev) + sqrt(1 - abar_prev) eps'.  cur_order 0: the first half of the Pseudo Improved Euler step
+// that opens a chain (:1136-1137), x_mid = pred sqrt(abar_prev) + sqrt(1 - abar_prev) eps -- from pred itself, not pred'.
+// Returns the sample (t != 0 ? mean : pred); *pred is x0-hat of this evaluation, *eps_out the eps the history takes (never eps').
+template <int MEAN = 0>
+__device__ __forceinline__ float plms_update(const StepCoef& c, float model_out, float x, bool has_blend, float mask, float motion,
+                                             bool clip, bool nonzero, int cur_order, float e1, float e2, float e3,
+                                             float* pred, float* eps_out) {
+    const float out = step_pred<MEAN>(c, model_out, x, has_blend, mask, motion, clip);
+    *pred = out;
+    const float eps = (c.srac * x - out) / c.srm1ac;
+    *eps_out = eps;
+    if (cur_order == 0) return out * c.sq_abp + c.dir * eps;
+    const float ep = plms_eps_prime(cur_order, eps, e1, e2, e3);
+    const float pp = c.srac * x - c.srm1ac * ep;
+    const float mean = pp * c.sq_abp + c.dir * ep;
+    return nonzero ? mean : out;
+}
+// The second half of the Euler step (:1138-1141): `model_out` is the model at (x_mid, t - 1), c1 the scalars at t - 1, c the ones at t,
+// x the chain's ORIGINAL input, eps the first evaluation's.  t >= 1 here, so the sample is the mean.
+template <int MEAN = 0>
+__device__ __forceinline__ float plms_euler(const StepCoef& c, const StepCoef& c1, float model_out, float x_mid, float x, float eps,
+                                            bool has_blend, float mask, float motion, bool clip) {
+    const float out2 = step_pred<MEAN>(c1, model_out, x_mid, has_blend, mask, motion, clip);
+    const float eps2 = (c1.srac * x_mid - out2) / c1.srm1ac;
+    const float ep = (eps + eps2) / 2.0f;
+    const float pp = c.srac * x - c.srm1ac * ep;
+    return pp * c.sq_abp + c.dir * ep;
+}
+
 // Per-call arguments of a sampling loop, kept in DEVICE memory: a captured step graph reads its tensors and its position in
 // the loop through this block, so one instantiated graph serves every later call with the same shapes (new clip tensors, new
 // seed) and every replay (the step counter `jbase` is advanced on the device at the end of each replay).
@@ -391,6 +455,9 @@ struct LoopDev {
     int up;                        // direction: 0 = step j visits index t_start - j (p_sample / ddim_sample), 1 = t_start + j (ddim_reverse_sample).
                                    // Read by the kernels that do not know the sampler (the pose embedding's conditioning token, CondTok); a
                                    // step kernel knows it from its MODE at compile time (step_resolve<UP>), so the descending ones are unchanged
+    // PLMS (read by the MODE 4 step kernels alone, plms_resolve): the fp32 eps ring [3][B,F,1,T] (slot stride `hist_stride` elements),
+    // the sampler's order and the chain steps taken before this call -- step j of the call is chain step k = steps_done + j
+    float* hist; unsigned long long hist_stride; int order; int steps_done;
 };
 
 // arguments of the fused diffusion step (output-projection epilogue)
@@ -431,6 +498,24 @@ __device__ __forceinline__ StepArgs step_resolve(StepArgs sa) {
     sa.xstart = sa.xstart ? d.xstart + (size_t)j * sa.step_stride + sa.eo : nullptr;
     sa.scale = sa.scale ? d.scale + sa.clip0 : nullptr;
     return sa;
+}
+
+// What a MODE 4 step reads at run time, so that ONE instantiation (and one captured graph) serves every order and every position in
+// a chain: chain step k has cur_order = min(order, k + 1) (the history then holds min(k, order - 1) entries), writes its eps into ring
+// slot k % 3 and reads e1 / e2 / e3 from slots (k - 1, k - 2, k - 3) % 3.  At cur_order 4 the slot written IS e3's: every element is read
+// and then written by the same thread.  `sa` is the resolved StepArgs (loop mode); the ring is addressed like x (offset `eo`).
+struct PlmsStep { int cur_order; float* ew; const float *e1, *e2, *e3; };
+__device__ __forceinline__ PlmsStep plms_resolve(const StepArgs& sa) {
+    const LoopDev& d = *sa.ld;
+    const int k = d.steps_done + (int)sa.step;
+    PlmsStep p;
+    p.cur_order = d.order < k + 1 ? d.order : k + 1;
+    float* h = d.hist ? d.hist + sa.eo : nullptr;          // (null: order 1 without a ring -- nothing is read, nothing kept)
+    p.ew = h ? h + (size_t)(k % 3) * d.hist_stride : nullptr;
+    p.e1 = h + (size_t)((k + 2) % 3) * d.hist_stride;
+    p.e2 = h + (size_t)((k + 1) % 3) * d.hist_stride;
+    p.e3 = p.ew;
+    return p;
 }
 
 namespace mst {

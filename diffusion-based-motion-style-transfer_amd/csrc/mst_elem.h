@@ -213,6 +213,53 @@ __global__ void k_step_epilogue(const float* __restrict__ tab, int nsteps, float
     }
 }
 
+// plms_sample stand-alone (gaussian_diffusion.py:1084-1166; model output produced elsewhere): the multistep step, cur_order 1..4
+// with the history newest first (e1, e2, e3; only cur_order - 1 of them are read), or -- cur_order 0 -- the first half of the Euler
+// step that opens a chain (sample = x_mid).  t: per-clip indices, or null and `t_uniform` for every clip (the native loop's warm-up).
+// No __restrict__ on the tensors a caller may alias element for element: eps_out on the oldest history slot (the ring at order 4),
+// sample on x (the warm-up writes x_mid in place); every element is read and then written by the same thread.
+template <int MEAN>
+__global__ void k_plms_epilogue(const float* __restrict__ tab, int nsteps, const float* __restrict__ model_out, const float* x,
+                                const float* __restrict__ mask, const float* __restrict__ motion, const long long* __restrict__ t,
+                                int t_uniform, long long per_clip, int clip_denoised, int cur_order, const float* e1, const float* e2,
+                                const float* e3, float* sample, float* __restrict__ xstart, float* eps_out, float* x_copy) {
+    const int clip = blockIdx.y;
+    const int ti = t ? (int)t[clip] : t_uniform;
+    const StepCoef sc = step_coef_plms(tab, nsteps, ti);
+    const bool blend = mask != nullptr && motion != nullptr;
+    const size_t base = (size_t)clip * per_clip;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < per_clip; i += (long long)gridDim.x * blockDim.x) {
+        const size_t idx = base + i;
+        const float m = blend ? mask[idx] : 0.f, mot = blend ? motion[idx] : 0.f;
+        const float h1 = cur_order >= 2 ? e1[idx] : 0.f, h2 = cur_order >= 3 ? e2[idx] : 0.f, h3 = cur_order >= 4 ? e3[idx] : 0.f;
+        const float xi = x[idx];
+        float pred, eps;
+        const float nx = plms_update<MEAN>(sc, model_out[idx], xi, blend, m, mot, clip_denoised, ti != 0, cur_order, h1, h2, h3, &pred, &eps);
+        if (x_copy) x_copy[idx] = xi;                       // (the warm-up keeps the chain's original input in ring slot 1)
+        if (sample) sample[idx] = nx;
+        if (xstart) xstart[idx] = pred;
+        if (eps_out) eps_out[idx] = eps;
+    }
+}
+// The second half of the Euler step (:1138-1141): model_out is the model at (x_mid, t - 1); x the chain's original input, eps the
+// first evaluation's.  Tables at t - 1 for eps2, at t for pred' and the mean.  sample may alias x_mid.
+template <int MEAN>
+__global__ void k_plms_euler(const float* __restrict__ tab, int nsteps, const float* __restrict__ model_out, const float* x_mid,
+                             const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ mask,
+                             const float* __restrict__ motion, const long long* __restrict__ t, int t_uniform, long long per_clip,
+                             int clip_denoised, float* sample) {
+    const int clip = blockIdx.y;
+    const int ti = t ? (int)t[clip] : t_uniform;
+    const StepCoef sc = step_coef_plms(tab, nsteps, ti), sc1 = step_coef_plms(tab, nsteps, ti - 1);
+    const bool blend = mask != nullptr && motion != nullptr;
+    const size_t base = (size_t)clip * per_clip;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < per_clip; i += (long long)gridDim.x * blockDim.x) {
+        const size_t idx = base + i;
+        const float m = blend ? mask[idx] : 0.f, mot = blend ? motion[idx] : 0.f;
+        sample[idx] = plms_euler<MEAN>(sc, sc1, model_out[idx], x_mid[idx], x[idx], eps[idx], blend, m, mot, clip_denoised);
+    }
+}
+
 // Backward of the fused step for the `*_with_grad` samplers (inpainting_gaussian_diffusion.py:66-123, :179-239): both
 // outputs are affine in the model output,
 //     pred   = out (1 - mask) + motion mask

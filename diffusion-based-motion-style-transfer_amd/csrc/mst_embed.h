@@ -94,6 +94,8 @@ __device__ __forceinline__ void emb_stream(const char* wsrc, unsigned w_voff, Be
 // of dependent loads); apply() -- the update itself (step_update, the same function as everywhere), stores, the next step's frame rows.
 // NU items per thread: item u = thread + 512 u, feature it / 16, frame group it % 16.
 // MODE 3 (the reverse step) has no noise term: noise1() is never called, load() reads no noise buffer, `nz` is never touched.
+// MODE 4 (the PLMS multistep step) has none either; its eps history is NOT held across the GEMM (up to three more f32x4 per item): apply()
+// loads the entries the step's cur_order needs item by item, in front of the item's tile read, and stores the item's eps into the ring.
 template <int MODE, int NU>
 struct OutItems {
     f32x4 nz[NU], xv[NU], mk1, mot1;          // (mk1, mot1): mask / motion of the thread's FIRST item that needs them, prefetched (item u1)
@@ -164,6 +166,8 @@ struct OutItems {
         const StepCoef sc = step_coef_for<step_sampler(MODE)>(sa.tab, sa.nsteps, sa.t, sa.eta);
         const bool blend = sa.mask != nullptr && sa.motion != nullptr, use_mask = sa.mask != nullptr;
         float* trow = tile + f0 * LDT + (threadIdx.x % TG) * 4;
+        PlmsStep ps{};
+        if constexpr (MODE == 4) ps = plms_resolve(sa);
 #pragma unroll
         for (int u = 0; u < NU; u++) {
             if (u >= nvalid) continue;
@@ -176,8 +180,28 @@ struct OutItems {
                     if (blend) mot = gload<f32x4>(sa.motion + idx);
                 }
             }
-            const f32x4 acc4 = *reinterpret_cast<const f32x4*>(trow + 32 * u * LDT);
             f32x4 nx, pred;
+            if constexpr (MODE == 4) {
+                f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h2 = h1, h3 = h1, ep;
+                if (ps.cur_order >= 2) h1 = gload<f32x4>(ps.e1 + idx);          // (wave-uniform: one cur_order per launch)
+                if (ps.cur_order >= 3) h2 = gload<f32x4>(ps.e2 + idx);
+                if (ps.cur_order >= 4) h3 = gload<f32x4>(ps.e3 + idx);
+                const f32x4 acc4 = *reinterpret_cast<const f32x4*>(trow + 32 * u * LDT);
+                const bool bl = blend && !(use_mask && rf[u] == 0);            // (an all-zero mask row: the blend is the identity)
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    float p, e;
+                    nx[j] = plms_update<0>(sc, acc4[j] + bu[u], xv[u][j], bl, mk[j], mot[j], sa.clip, sa.t != 0, ps.cur_order, h1[j], h2[j], h3[j], &p, &e);
+                    pred[j] = p;
+                    ep[j] = e;
+                }
+                gstore(sa.sample + idx, nx);
+                if (sa.xstart) gstore(sa.xstart + idx, pred);
+                if (ps.ew) gstore(ps.ew + idx, ep);
+                if (epi.xt_next) *reinterpret_cast<f32x4*>(trow + 32 * u * LDT) = nx;
+                continue;
+            }
+            const f32x4 acc4 = *reinterpret_cast<const f32x4*>(trow + 32 * u * LDT);
             if (use_mask && rf[u] == 0) {
                 // the row's mask is all zeros: out (1 - 0) + motion 0 and noise (1 - 0) are the identity -- the same values without the
                 // blend arithmetic (most rows: all but 3 of 263 with the root pattern)

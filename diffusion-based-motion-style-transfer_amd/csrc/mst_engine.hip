@@ -248,6 +248,7 @@ struct mst_engine {
     // sampling-loop state in device memory + the captured step graph (mst_sample_loop)
     LoopDev* ld_dev = nullptr;
     unsigned char* rowflag = nullptr;     // [max_rows][feats] summary of the loop's inpainting mask (k_mask_rowflags)
+    float* plms_out = nullptr;            // [max_rows][feats][max_frames] model output of the PLMS warm-up's two evaluations (first PLMS chain allocates it)
     LoopDev* ld_pin = nullptr;            // pinned staging ring for the per-call upload
     static constexpr int LD_SLOTS = 8;
     hipEvent_t ld_ev[LD_SLOTS] = {nullptr};
@@ -494,6 +495,7 @@ extern "C" void mst_engine_destroy(mst_engine* e) {
     if (e->ev_out) (void)hipEventDestroy(e->ev_out);
     (void)hipFree(e->ld_dev);
     (void)hipFree(e->rowflag);
+    (void)hipFree(e->plms_out);
     if (e->ld_pin) (void)hipHostFree(e->ld_pin);
     for (LayerW& w : e->slot_w) {
         void* q[] = {w.b_in, w.b_out, w.b1, w.b2, w.g1, w.be1, w.g2, w.be2, w.wtail, w.wqkv, w.wsm_in, w.wsm_out, w.wsm_1, w.wsm_2};
@@ -1833,7 +1835,7 @@ static int enqueue_step(mst_engine* e, const LoopPlan& p, int joff, int nsj, boo
         const float* const yes = reinterpret_cast<const float*>(1);
         sa.mask = a->inpainting_mask_dev ? yes : nullptr;
         sa.motion = a->inpainted_motion_dev ? yes : nullptr;
-        const bool draws = a->sampler != MST_SAMPLER_DDIM_REVERSE;      // the reverse step has no noise term: noise_mode, seed, noise_dev, mask_noise are not read
+        const bool draws = a->sampler != MST_SAMPLER_DDIM_REVERSE && a->sampler != MST_SAMPLER_PLMS;      // the reverse and PLMS steps have no noise term: noise_mode, seed, noise_dev, mask_noise are not read
         sa.noise = draws && a->noise_mode == MST_NOISE_BUFFER ? yes : nullptr;
         sa.scale = a->scale_dev ? yes : nullptr;
         sa.xstart = a->xstart_dump_dev ? reinterpret_cast<float*>(1) : nullptr;
@@ -1848,7 +1850,54 @@ static int enqueue_step(mst_engine* e, const LoopPlan& p, int joff, int nsj, boo
         sa.rowflag = (a->inpainting_mask_dev && a->inpainted_motion_dev) ? e->rowflag + (size_t)c0 * e->cfg.feats : nullptr;
         if (a->sampler == MST_SAMPLER_DDPM) CHECK(launch_out_nt<1>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
         else if (a->sampler == MST_SAMPLER_DDIM_REVERSE) CHECK(launch_out_nt<3>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
+        else if (a->sampler == MST_SAMPLER_PLMS) CHECK(launch_out_nt<4>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
         else CHECK(launch_out_nt<2>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
+    }
+    return 0;
+}
+// The step that opens a PLMS chain of order > 1 (Pseudo Improved Euler, gaussian_diffusion.py:1134-1141): once per chain, so not fused.
+// Per slice, on its stream: the model at (x, t_start) through the model-output-only projection (MODE 0), k_plms_epilogue's first half
+// (x <- x_mid, ring slot 0 <- eps, x0-hat dump entry 0 <- pred, ring slot 1 <- the original x: free until chain step 1 writes it), the
+// model at (x_mid, t_start - 1) -- the loop's step 1 as far as the conditioning token is concerned -- and k_plms_euler (x <- the sample).
+// Always enqueued from the host; the step behind it starts from x in memory (no chained frame rows, no pre-embedded stream).
+static int enqueue_plms_warmup(mst_engine* e, const LoopPlan& p, const mst_plms_args* pl) {
+    const mst_loop_args* a = p.a;
+    e->cur_slices = p.nsl;
+    const int gx = (int)((p.per_clip + 255) / 256);
+    for (int sl = 0; sl < p.nsl; sl++) {
+        const int per = (a->batch + p.nsl - 1) / p.nsl;
+        const int c0 = sl * per;
+        const int nb = (c0 + per <= a->batch) ? per : a->batch - c0;
+        if (nb <= 0) continue;
+        const size_t eo = (size_t)c0 * p.per_clip;
+        WS ws = ws_slice(e, a->cfg ? 2 * c0 : c0, a->frames);
+        ws.textproj = e->textproj + (size_t)c0 * MST_D;
+        hipStream_t ss = p.streams[sl];
+        float* const out = e->plms_out + eo;
+        float* const x = a->x_dev + eo;
+        float* const h0 = pl->hist_dev + eo;
+        float* const h1 = h0 + p.clip_elems;
+        const bool blend = a->inpainting_mask_dev && a->inpainted_motion_dev;
+        const float* const mask = blend ? a->inpainting_mask_dev + eo : nullptr;
+        const float* const motion = blend ? a->inpainted_motion_dev + eo : nullptr;
+        for (int half = 0; half < 2; half++) {
+            LoopRef lr{e->ld_dev, half, eo, false, false};
+            e->style_cur = styles_on(e) ? &e->plan_sl[sl] : nullptr;
+            const int rc = run_trunk(e, ws, nullptr, nb, a->cfg ? 2 * nb : nb, a->frames, 0, 0, ss, a->batch, lr);
+            e->style_cur = nullptr;
+            CHECK(rc);
+            StepArgs sa{};
+            sa.scale = a->scale_dev ? a->scale_dev + c0 : nullptr;
+            CHECK(launch_out_nt<0>(e, ws, a->cfg, nb, a->frames, out, sa, ss, nullptr, nullptr, 1, false, true));
+            if (half == 0)
+                hipLaunchKernelGGL(k_plms_epilogue<0>, dim3(gx, nb), dim3(256), 0, ss, p.s->tab, p.s->n, out, x, mask, motion, (const long long*)nullptr,
+                                   a->t_start, (long long)p.per_clip, a->clip_denoised, 0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                                   x, a->xstart_dump_dev ? a->xstart_dump_dev + eo : nullptr, h0, h1);
+            else
+                hipLaunchKernelGGL(k_plms_euler<0>, dim3(gx, nb), dim3(256), 0, ss, p.s->tab, p.s->n, out, x, h1, h0, mask, motion, (const long long*)nullptr,
+                                   a->t_start, (long long)p.per_clip, a->clip_denoised, x);
+            HIPCHECK(hipGetLastError());
+        }
     }
     return 0;
 }
@@ -1869,10 +1918,13 @@ static int join_slices(mst_engine* e, const LoopPlan& p) {
 // (short loops, instrumented runs) or replayed from a captured hipGraph of `graph_steps` steps: every kernel reads its
 // tensors and its step index through the LoopDev block in device memory, which a one-thread kernel at the end of the graph
 // advances, so the instantiated graph is reused by every replay and by every later call with the same shapes.
-extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, void* stream) {
+// pl: the PLMS chain state (mst_sample_loop_plms; a->sampler is then MST_SAMPLER_PLMS), null for every other sampler.
+static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_plms_args* pl, void* stream) {
     if (!s || !a) return fail("mst_sample_loop: null argument");
     CHECK(check_ready(e, a->batch, a->frames, a->cfg));
-    if (a->sampler != MST_SAMPLER_DDPM && a->sampler != MST_SAMPLER_DDIM && a->sampler != MST_SAMPLER_DDIM_REVERSE)
+    if (a->sampler == MST_SAMPLER_PLMS && !pl)
+        return fail("mst_sample_loop: bad sampler %d: MST_SAMPLER_PLMS carries a history between steps, call mst_sample_loop_plms", a->sampler);
+    if (a->sampler != MST_SAMPLER_DDPM && a->sampler != MST_SAMPLER_DDIM && a->sampler != MST_SAMPLER_DDIM_REVERSE && a->sampler != MST_SAMPLER_PLMS)
         return fail("mst_sample_loop: bad sampler %d", a->sampler);
     const bool up = a->sampler == MST_SAMPLER_DDIM_REVERSE;      // ddim_reverse_sample: ascending indices, no noise term
     if (up) {
@@ -1883,10 +1935,13 @@ extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_l
     } else if (a->t_start >= s->n || a->t_end < 0 || a->t_start < a->t_end)
         return fail("mst_sample_loop: bad index range %d..%d for %d steps", a->t_start, a->t_end, s->n);
     if (!a->x_dev || (a->cfg && !a->scale_dev)) return fail("mst_sample_loop: null x / scale");
-    if (!up && a->noise_mode == MST_NOISE_BUFFER && !a->noise_dev) return fail("mst_sample_loop: noise buffer missing");
+    if (!up && !pl && a->noise_mode == MST_NOISE_BUFFER && !a->noise_dev) return fail("mst_sample_loop: noise buffer missing");
     if (styles_on(e)) CHECK(style_check(e, a->batch, a->frames));
     hipStream_t caller = (hipStream_t)stream;
     ON_DEVICE(e->cfg.device);
+    // a PLMS chain of order > 1 opens with the two-evaluation Euler step (enqueue_plms_warmup)
+    const bool warm = pl && pl->steps_done == 0 && pl->order > 1;
+    if (warm && !e->plms_out) CHECK(dmalloc(&e->plms_out, (size_t)e->cfg.max_rows * e->cfg.feats * e->cfg.max_frames));
     // The loop runs on engine-owned streams: behind everything the caller has enqueued (ev_in), and the caller's stream
     // continues behind the loop (ev_out).  A captured graph needs that: torch's current stream is normally the legacy
     // default stream, which cannot be captured.
@@ -1898,7 +1953,9 @@ extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_l
     // reads row nrun - 1 - j, an ascending one row j -- CondTok)
     e->prof_now = 0;
     CHECK(ensure_packed(e, st));
-    CHECK(timestep_rows(e, s->tmap + (up ? a->t_start : a->t_end), nrun, st));
+    // (a PLMS warm-up evaluates the model at t_start - 1 as well: a one-step call then hoists two rows)
+    const int trows = warm && nrun < 2 ? 2 : nrun;
+    CHECK(timestep_rows(e, s->tmap + (up ? a->t_start : a->t_start - trows + 1), trows, st));
     // Clips are independent, so the batch runs as `nsplit` slices on separate streams: one slice's kernels fill
     // the CUs the other leaves idle in its prologues, tails and launch gaps (per-launch time is per-CU bound and
     // flat in the block count at this size).  CFG batches are sliced the same way (cond + uncond twins stay together).
@@ -1912,7 +1969,8 @@ extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_l
         HIPCHECK(hipEventSynchronize(e->ld_ev[slot]));
         LoopDev& h = e->ld_pin[slot];
         h = LoopDev{a->x_dev, a->inpainting_mask_dev, a->inpainted_motion_dev, a->noise_dev, a->scale_dev, a->xstart_dump_dev,
-                    a->seed, a->eta, a->t_start, nrun, 0, up ? 1 : 0};
+                    a->seed, a->eta, a->t_start, trows, 0, up ? 1 : 0,
+                    pl ? pl->hist_dev : nullptr, (unsigned long long)p.clip_elems, pl ? pl->order : 0, pl ? pl->steps_done : 0};
         HIPCHECK(hipMemcpyAsync(e->ld_dev, &h, sizeof(LoopDev), hipMemcpyHostToDevice, st));
         HIPCHECK(hipEventRecord(e->ld_ev[slot], st));
     }
@@ -1927,16 +1985,23 @@ extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_l
                                   a->inpainting_mask_dev != nullptr, a->inpainted_motion_dev != nullptr, a->xstart_dump_dev != nullptr,
                                   a->scale_dev != nullptr, p.nsl, U, (long long)(size_t)s->tab, s->n, e->small_m, e->fuse_tail,
                                   e->fuse_qkv_attn, e->ln128_min_m, e->precise, e->tail_ntb, e->embed_fast, e->small_fast, e->small_ln};      // every switch run_trunk / loop_slices_for branch on
-    const bool use_graph = e->graph_on && !e->prof_on && e->dbg_stage < 0 && nrun >= 2 * U;
+    const int j0 = warm ? 1 : 0;                              // the warm-up is the call's step 0
+    const bool use_graph = e->graph_on && !e->prof_on && e->dbg_stage < 0 && nrun - j0 >= 2 * U;
     bool forked = false;
     auto steps = [&]() -> int {
         int j = 0;
+        if (warm) {
+            if (p.nsl > 1) { CHECK(fork_slices(e, p)); forked = true; }
+            CHECK(enqueue_plms_warmup(e, p, pl));
+            j = 1;
+        }
         if (use_graph) {
             // head of the loop from the host: the remainder, plus one graph's worth of steps the first time a configuration is
             // seen (every kernel's per-device LDS opt-in must have happened before a capture)
-            int pre = nrun % U;
+            int pre = (nrun - j0) % U;
             if (e->warm_key != key) pre += U;
-            if (p.nsl > 1) { CHECK(fork_slices(e, p)); forked = true; }
+            pre += j0;
+            if (p.nsl > 1 && !forked) { CHECK(fork_slices(e, p)); forked = true; }
             for (; j < pre; j++) CHECK(enqueue_step(e, p, j, p.nsl));
             if (forked) { CHECK(join_slices(e, p)); forked = false; }
             e->warm_key = key;
@@ -1986,7 +2051,7 @@ extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_l
             if (nsj > 1 && !forked) { CHECK(fork_slices(e, p)); forked = true; }
             else if (nsj == 1 && forked) { CHECK(join_slices(e, p)); forked = false; }
             const bool embed_next = fuse_embed && j + 1 < nrun && !instrumented(j) && !instrumented(j + 1);
-            CHECK(enqueue_step(e, p, j, nsj, chain && j > 0 && !stream_ready, chain && j + 1 < nrun && !embed_next, stream_ready, embed_next));
+            CHECK(enqueue_step(e, p, j, nsj, chain && j > j0 && !stream_ready, chain && j + 1 < nrun && !embed_next, stream_ready, embed_next));
             stream_ready = embed_next;
         }
         return 0;
@@ -2002,6 +2067,27 @@ extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_l
     e->prof_now = 0;
     if (hipEventRecord(e->ev_out, st) == hipSuccess) (void)hipStreamWaitEvent(caller, e->ev_out, 0);
     return trunk_settle(e, st, rc);
+}
+
+extern "C" int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, void* stream) {
+    return sample_loop_run(e, s, a, nullptr, stream);
+}
+
+extern "C" int mst_sample_loop_plms(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_plms_args* pl, void* stream) {
+    if (!s || !a || !pl) return fail("mst_sample_loop_plms: null argument");
+    if (pl->order < 1 || pl->order > 4) return fail("mst_sample_loop_plms: order %d is invalid (should be int from 1-4)", pl->order);
+    if (pl->steps_done < 0) return fail("mst_sample_loop_plms: steps_done %d is negative", pl->steps_done);
+    if (pl->order > 1 && !pl->hist_dev) return fail("mst_sample_loop_plms: order %d needs the eps history ring (hist_dev is NULL)", pl->order);
+    if (pl->order > 1 && pl->steps_done == 0 && a->t_start == 0)
+        return fail("mst_sample_loop_plms: a chain of order %d cannot start at index 0: its first step evaluates the model at index t - 1", pl->order);
+    mst_loop_args b = *a;
+    b.sampler = MST_SAMPLER_PLMS;
+    b.eta = 0.0f;
+    b.noise_mode = MST_NOISE_PHILOX;                         // (no noise term: nothing is drawn, no buffer is read)
+    b.noise_dev = nullptr;
+    b.seed = 0;
+    b.mask_noise = 0;
+    return sample_loop_run(e, s, &b, pl, stream);
 }
 
 // ------------------------------------------------------------------------------------------ elementwise ABI
@@ -2051,6 +2137,45 @@ extern "C" int mst_step_epilogue(const mst_schedule* s, const float* model_out, 
                                 xstart, stream);
 }
 
+// plms_sample given the model output (gaussian_diffusion.py:1084-1166).  first_half: the first half of the Euler step instead.
+extern "C" int mst_plms_epilogue(const mst_schedule* s, const float* model_out, const float* x, const float* mask, const float* motion,
+                                 const int64_t* t, int32_t batch, int64_t per_clip, int32_t mean_type, int32_t clip_denoised, int32_t cur_order,
+                                 int32_t first_half, const float* e1, const float* e2, const float* e3, float* sample, float* xstart,
+                                 float* eps_out, void* stream) {
+    if (!s || !model_out || !x || !t || batch < 1 || per_clip < 1) return fail("mst_plms_epilogue: bad arguments");
+    if (mean_type < 0 || mean_type > 2) return fail("mst_plms_epilogue: bad mean type %d (0 = x_start, 1 = epsilon, 2 = previous x)", mean_type);
+    if (!first_half) {
+        if (cur_order < 1 || cur_order > 4) return fail("mst_plms_epilogue: cur_order %d is invalid (should be int from 1-4)", cur_order);
+        if ((cur_order >= 2 && !e1) || (cur_order >= 3 && !e2) || (cur_order >= 4 && !e3))
+            return fail("mst_plms_epilogue: cur_order %d needs %d history entries", cur_order, cur_order - 1);
+    }
+    ON_DEVICE(s->device);
+    const int gx = (int)((per_clip + 255) / 256), co = first_half ? 0 : cur_order;
+#define PLMS_LAUNCH(M_)                                                                                                                  \
+    hipLaunchKernelGGL(k_plms_epilogue<M_>, dim3(gx, batch), dim3(256), 0, (hipStream_t)stream, s->tab, s->n, model_out, x, mask, motion, \
+                       (const long long*)t, 0, (long long)per_clip, clip_denoised, co, e1, e2, e3, sample, xstart, eps_out, (float*)nullptr)
+    switch (mean_type) { case 0: PLMS_LAUNCH(0); break; case 1: PLMS_LAUNCH(1); break; default: PLMS_LAUNCH(2); break; }
+#undef PLMS_LAUNCH
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+// The second half of the Euler step: model_out is the model at (x_mid, t - 1); t holds the step's own indices (every one >= 1).
+extern "C" int mst_plms_euler(const mst_schedule* s, const float* model_out, const float* x_mid, const float* x, const float* eps,
+                              const float* mask, const float* motion, const int64_t* t, int32_t batch, int64_t per_clip, int32_t mean_type,
+                              int32_t clip_denoised, float* sample, void* stream) {
+    if (!s || !model_out || !x_mid || !x || !eps || !t || !sample || batch < 1 || per_clip < 1) return fail("mst_plms_euler: bad arguments");
+    if (mean_type < 0 || mean_type > 2) return fail("mst_plms_euler: bad mean type %d (0 = x_start, 1 = epsilon, 2 = previous x)", mean_type);
+    ON_DEVICE(s->device);
+    const int gx = (int)((per_clip + 255) / 256);
+#define EULER_LAUNCH(M_)                                                                                                                 \
+    hipLaunchKernelGGL(k_plms_euler<M_>, dim3(gx, batch), dim3(256), 0, (hipStream_t)stream, s->tab, s->n, model_out, x_mid, x, eps, mask, \
+                       motion, (const long long*)t, 0, (long long)per_clip, clip_denoised, sample)
+    switch (mean_type) { case 0: EULER_LAUNCH(0); break; case 1: EULER_LAUNCH(1); break; default: EULER_LAUNCH(2); break; }
+#undef EULER_LAUNCH
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int mst_step_backward(const mst_schedule* s, const float* g_sample, const float* g_pred, const float* mask,
                                  int32_t has_blend, const int64_t* t, int32_t batch, int64_t per_clip, int32_t sampler, float eta,
                                  const float* pred_clipped, float* d_model_out, void* stream) {
@@ -2067,6 +2192,8 @@ extern "C" int mst_step_backward(const mst_schedule* s, const float* g_sample, c
                            has_blend, (const long long*)t, (long long)per_clip, pred_clipped, d_model_out);
     else if (sampler == MST_SAMPLER_DDIM_REVERSE)
         return fail("mst_step_backward: MST_SAMPLER_DDIM_REVERSE has no backward: the reference has no _with_grad form of ddim_reverse_sample");
+    else if (sampler == MST_SAMPLER_PLMS)
+        return fail("mst_step_backward: MST_SAMPLER_PLMS has no backward: the reference has no _with_grad form of plms_sample");
     else
         return fail("mst_step_backward: bad sampler %d", sampler);
     HIPCHECK(hipGetLastError());

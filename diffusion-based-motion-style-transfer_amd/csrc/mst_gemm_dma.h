@@ -589,7 +589,8 @@ struct DEpiEmbedIn {
 // tensors are frame-contiguous, so a wave touches 256-B runs.  (First version: per-lane scalar gathers
 // straight from the accumulator layout, all work in 4-5 of the 8 waves: 36 us even at batch 16.)
 // MODE 0 model output only, 1 ancestral step, 2 DDIM step, 3 DDIM reverse step (x_t -> x_{t+1}: no noise term, so no draw, no noise
-// load and no noise mask in its instantiations); NX = 2 is the CFG doubled batch.
+// load and no noise mask in its instantiations), 4 PLMS multistep step (plms_update: no noise term either; cur_order and the eps ring
+// come from the loop block at run time, plms_resolve); NX = 2 is the CFG doubled batch.
 template <int MODE>
 struct DEpiEmbedOut {
     const float* bias; int F, T, total; float* out; StepArgs sa;
@@ -603,6 +604,16 @@ struct DEpiEmbedOut {
         if (MODE == 0) { out[idx] = mo; return; }
         const float mk = use_mask ? sa.mask[idx] : 0.f, mot = blend ? sa.motion[idx] : 0.f;
         float pred;
+        if constexpr (MODE == 4) {                             // the PLMS multistep step, element-wise (frame counts that are no multiple of 4)
+            const PlmsStep ps = plms_resolve(sa);
+            const float h1 = ps.cur_order >= 2 ? ps.e1[idx] : 0.f, h2 = ps.cur_order >= 3 ? ps.e2[idx] : 0.f, h3 = ps.cur_order >= 4 ? ps.e3[idx] : 0.f;
+            float e;
+            const float nx = plms_update<0>(sc, mo, sa.x[idx], blend, mk, mot, sa.clip, sa.t != 0, ps.cur_order, h1, h2, h3, &pred, &e);
+            sa.sample[idx] = nx;
+            if (sa.xstart) sa.xstart[idx] = pred;
+            if (ps.ew) ps.ew[idx] = e;
+            return;
+        }
         const float nx = step_update<step_sampler(MODE)>(sc, mo, sa.x[idx], nz, blend, mk, mot, sa.mask_noise && use_mask, sa.clip, &pred);
         sa.sample[idx] = nx;
         if (sa.xstart) sa.xstart[idx] = pred;
@@ -645,6 +656,8 @@ struct DEpiEmbedOut {
         const bool philox = step_draws(MODE) && sa.philox;
         const bool vec = (T & 3) == 0;                       // 4 consecutive frames never straddle a clip
         constexpr int TG = BT / 4;
+        PlmsStep ps{};
+        if constexpr (MODE == 4) ps = plms_resolve(sa);
         if (vec && MODE != 0) {
             // Three items per thread and pass, loads first: one item at a time the loop is a chain of dependent global loads (x, the row
             // flag, then mask / motion) per iteration, nine iterations deep at F = 263 -- latency, not bandwidth.
@@ -698,11 +711,26 @@ struct DEpiEmbedOut {
                         for (int j = 0; j < 4; j++) nz[u][j] = nrm[j];
                     }
                     f32x4 nx, pred;
+                    if constexpr (MODE == 4) {
+                        f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h2 = h1, h3 = h1, ep;
+                        if (ps.cur_order >= 2) h1 = *reinterpret_cast<const f32x4*>(ps.e1 + idx[u]);
+                        if (ps.cur_order >= 3) h2 = *reinterpret_cast<const f32x4*>(ps.e2 + idx[u]);
+                        if (ps.cur_order >= 4) h3 = *reinterpret_cast<const f32x4*>(ps.e3 + idx[u]);
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            float p, e;
+                            nx[j] = plms_update<0>(sc, mo[j], xv[u][j], blend, mk[u][j], mot[u][j], sa.clip, sa.t != 0, ps.cur_order, h1[j], h2[j], h3[j], &p, &e);
+                            pred[j] = p;
+                            ep[j] = e;
+                        }
+                        if (ps.ew) *reinterpret_cast<f32x4*>(ps.ew + idx[u]) = ep;
+                    } else {
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         float p;
                         nx[j] = step_update<step_sampler(MODE)>(sc, mo[j], xv[u][j], nz[u][j], blend, mk[u][j], mot[u][j], sa.mask_noise && use_mask, sa.clip, &p);
                         pred[j] = p;
+                    }
                     }
                     *reinterpret_cast<f32x4*>(sa.sample + idx[u]) = nx;
                     if (sa.xstart) *reinterpret_cast<f32x4*>(sa.xstart + idx[u]) = pred;

@@ -2,7 +2,8 @@
 
 Same public names, signatures and numpy float64 tables as the reference (GaussianDiffusion
 :111-221, q_sample :267-285, p_mean_variance :311-424, p_sample :532-585, p_sample_loop(_progressive)
-:644-794, ddim_sample :796-860, ddim_reverse_sample :910-946, ddim_sample_loop(_progressive) :948-1082, masked_l2 :223-235,
+:644-794, ddim_sample :796-860, ddim_reverse_sample :910-946, ddim_sample_loop(_progressive) :948-1082, plms_sample and
+plms_sample_loop(_progressive) :1084-1279, masked_l2 :223-235,
 _extract_into_tensor :1605-1618, schedules :22-66), but the arithmetic runs in the HIP library:
 
   * model is an engine-backed denoiser (mst_amd.model.StyleDiffusion / MDM, optionally wrapped in
@@ -605,6 +606,155 @@ class GaussianDiffusion:
         dump, final = [], None
         for out in self._steps_from(_eng.SAMPLER_DDIM, model, device, x_t.to(device), list(range(n))[::-1], clip_denoised, denoised_fn,
                                     cond_fn, model_kwargs, False, eta, progress, True, bool(dump_all_xstart)):
+            if dump_all_xstart:
+                dump.append(out["pred_xstart"])
+            final = out
+        return dump if dump_all_xstart else final["sample"]
+
+    # -- PLMS (reference :1084-1279): Pseudo Linear Multistep, orders 1..4.  No noise term: nothing is drawn anywhere below.
+    def plms_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                    cond_fn_with_grad=False, order=2, old_out=None):
+        """One PLMS step (reference :1084-1166) for any model callable, through the stand-alone kernels (mst_plms_epilogue,
+        mst_plms_euler).  Returns {"sample", "pred_xstart", "old_eps"}: `old_eps` is the list the caller passed in `old_out`
+        (newest last, at most order - 1 long), mutated as the reference mutates it -- this step's eps appended, the oldest dropped --
+        or, for the step that opens a chain (`old_out=None`, order > 1: the two-evaluation Pseudo Improved Euler step), a new list.
+        Departure from the reference: that opening step at index 0 raises ValueError (the reference evaluates the model at
+        t - 1 = -1 there, which wraps to the last table entry)."""
+        if not int(order) or not 1 <= order <= 4:
+            raise ValueError('order is invalid (should be int from 1-4).')
+        if cond_fn is not None or denoised_fn is not None:
+            raise NotImplementedError("cond_fn / denoised_fn are never set by this code base (SURVEY.md section 9)")
+        sch = self._schedule(x.device)
+        mask, motion = self._inpaint_pair(model_kwargs)
+        mean_type = {ModelMeanType.START_X: 0, ModelMeanType.EPSILON: 1, ModelMeanType.PREVIOUS_X: 2}[self.model_mean_type]
+        kw = dict(mask=mask, motion=motion, clip_denoised=clip_denoised, mean_type=mean_type)
+        with th.no_grad():
+            out = self._model_output(model, x, t, model_kwargs)
+            if order > 1 and old_out is None:
+                if bool((t == 0).any()):
+                    raise ValueError("plms_sample: a chain of order > 1 cannot start at index 0 (its first step evaluates the model at t - 1)")
+                x_mid, pred, eps = sch.plms_step(out, x, t, first_half=True, **kw)
+                out2 = self._model_output(model, x_mid, t - 1, model_kwargs)
+                sample = sch.plms_euler(out2, x_mid, x, eps, t, **kw)
+                old_eps = [eps]
+            else:
+                old_eps = old_out["old_eps"]
+                sample, pred, eps = sch.plms_step(out, x, t, history=old_eps, order=order, **kw)
+                old_eps.append(eps)
+        if len(old_eps) >= order:
+            old_eps.pop(0)
+        return {"sample": sample, "pred_xstart": pred, "old_eps": old_eps}
+
+    def _plms_engine_loop(self, denoiser, cfg, img, indices, clip_denoised, model_kwargs, order, progress, chunked, want_xstart):
+        """The PLMS loop inside the library (mst_sample_loop_plms): the eps history lives in a [3,B,F,1,T] ring that the calls of
+        one chain share, `steps_done` carried from call to call.  chunked / want_xstart as `_engine_loop`; a yielded 'old_eps' is a
+        list of clones taken from the ring, oldest first (None for the intermediate entries of a chunked loop)."""
+        y = self._y(model_kwargs)
+        eng = denoiser.mst_engine(img.shape[0] * (2 if cfg is not None else 1), img.shape[-1])
+        denoiser.mst_prepare(eng, y, cfg is not None)
+        mask, motion = self._inpaint_pair(model_kwargs)
+        scale = y['scale'] if cfg is not None else None
+        sch = self._schedule(img.device)
+        x = img.contiguous().float().clone()
+        hist = th.empty((3,) + tuple(x.shape), dtype=th.float32, device=x.device) if order > 1 else None
+        if not chunked:
+            chunk = 1
+        else:
+            chunk = len(indices) if not want_xstart else max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
+        if cfg is not None:
+            eng.check_guidance_scale(scale)
+        it = range(0, len(indices), chunk)
+        if progress:
+            from tqdm.auto import tqdm
+            it = tqdm(it)
+        for c0 in it:
+            idx = indices[c0:c0 + chunk]
+            res = eng.sample_loop_plms(sch, x, idx[0], idx[-1], order=order, steps_done=c0, hist=hist, cfg=cfg is not None, scale=scale,
+                                       mask=mask, motion=motion, clip_denoised=clip_denoised, dump_xstart=want_xstart)
+            dump = res[1] if want_xstart else None
+            for j in range(len(idx)):
+                end = j == len(idx) - 1
+                k = c0 + j                                          # the chain step just taken: the ring holds steps k - held + 1 .. k
+                held = min(k + 1, order - 1)
+                yield {"sample": (x if chunked else x.clone()) if end else None,
+                       "pred_xstart": dump[j] if want_xstart else None,
+                       "old_eps": [hist[i % 3].clone() for i in range(k - held + 1, k + 1)] if end else None}
+
+    def _plms_steps_from(self, model, device, img, indices, clip_denoised, denoised_fn, cond_fn, model_kwargs, cond_fn_with_grad, order,
+                         progress, chunked, want_xstart):
+        """The steps of every PLMS loop entry from `img` as it is through the descending `indices`: inside the library under the
+        condition `_steps_from` uses, step by step through `plms_sample` otherwise."""
+        if not int(order) or not 1 <= order <= 4:
+            raise ValueError('order is invalid (should be int from 1-4).')
+        if cond_fn is not None or denoised_fn is not None:
+            raise NotImplementedError("cond_fn / denoised_fn are never set by this code base (SURVEY.md section 9)")
+        if order > 1 and indices[0] == 0:
+            raise ValueError("plms_sample_loop: a chain of order > 1 cannot start at index 0 (its first step evaluates the model at t - 1)")
+        denoiser, cfg, _ = _unwrap(model)
+        if denoiser is not None and not denoiser.training and self.model_mean_type == ModelMeanType.START_X:
+            yield from self._plms_engine_loop(denoiser, cfg, img, indices, clip_denoised, model_kwargs, int(order), progress, chunked,
+                                              want_xstart)
+            return
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        old_out = {"old_eps": []} if order == 1 else None      # (the reference's loop raises TypeError at order 1: old_out is None there)
+        for i in indices:
+            t = th.full((img.shape[0],), int(i), device=device, dtype=th.long)
+            with th.no_grad():
+                out = self.plms_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                       model_kwargs=model_kwargs, cond_fn_with_grad=cond_fn_with_grad, order=order, old_out=old_out)
+                yield out
+                old_out = out
+                img = out["sample"]
+
+    def plms_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                     model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
+                                     randomize_class=False, cond_fn_with_grad=False, order=2):
+        """PLMS at every index, one dict per step (reference :1210-1279).  The dict's 'old_eps' is the history after the step, newest
+        last: the live list when the model is stepped from Python (as in the reference, later steps mutate it), clones taken from the
+        native loop's ring otherwise.  Departures from the reference, all three where it fails: order=1 starts from an empty history
+        (the reference raises TypeError); q_sample of an init image receives model_kwargs, as the other loops pass it (under
+        InpaintingGaussianDiffusion the reference raises TypeError); a chain that starts at index 0 with order > 1 raises ValueError
+        (the reference reads the tables at index -1)."""
+        yield from self._plms_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, skip_timesteps,
+                                   init_image, randomize_class, cond_fn_with_grad, order, False, True)
+
+    def _plms_loop(self, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, skip_timesteps,
+                   init_image, randomize_class, cond_fn_with_grad, order, chunked, want_xstart):
+        if randomize_class:
+            raise NotImplementedError("randomize_class is an image-diffusion leftover, unused by this model family")
+        if not int(order) or not 1 <= order <= 4:
+            raise ValueError('order is invalid (should be int from 1-4).')
+        if cond_fn is not None or denoised_fn is not None:
+            raise NotImplementedError("cond_fn / denoised_fn are never set by this code base (SURVEY.md section 9)")
+        if order > 1 and self.num_timesteps - skip_timesteps - 1 == 0:
+            raise ValueError("plms_sample_loop: a chain of order > 1 cannot start at index 0 (its first step evaluates the model at t - 1)")
+        device, img, indices = self._loop_setup(model, shape, noise, device, skip_timesteps, init_image, None, model_kwargs)
+        yield from self._plms_steps_from(model, device, img, indices, clip_denoised, denoised_fn, cond_fn, model_kwargs,
+                                         cond_fn_with_grad, order, progress, chunked, want_xstart)
+
+    def plms_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                         device=None, progress=False, skip_timesteps=0, init_image=None, randomize_class=False,
+                         cond_fn_with_grad=False, order=2):
+        """The final sample of plms_sample_loop_progressive (reference :1168-1208; the same three departures)."""
+        final = None
+        for out in self._plms_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
+                                   skip_timesteps, init_image, randomize_class, cond_fn_with_grad, order, True, False):
+            final = out
+        return final["sample"]
+
+    def plms_sample_loop_from(self, model, x_t, num_steps, order=2, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                              model_kwargs=None, device=None, progress=False, dump_all_xstart=False):
+        """plms_sample at indices num_steps - 1 .. 0 starting from `x_t` AS IT IS (no q_sample, no initial draw): the PLMS twin of
+        ddim_sample_loop_from, the decode half of a (partial) inversion.  An addition: the reference has no such entry."""
+        n = int(num_steps)
+        if not 1 <= n <= self.num_timesteps:
+            raise ValueError(f"plms_sample_loop_from: num_steps {n} outside 1..{self.num_timesteps}")
+        device = self._loop_device(model, device)
+        dump, final = [], None
+        for out in self._plms_steps_from(model, device, x_t.to(device), list(range(n))[::-1], clip_denoised, denoised_fn, cond_fn,
+                                         model_kwargs, False, order, progress, True, bool(dump_all_xstart)):
             if dump_all_xstart:
                 dump.append(out["pred_xstart"])
             final = out

@@ -12,6 +12,8 @@ from . import _native as N
 
 SAMPLER_DDPM, SAMPLER_DDIM = 0, 1
 SAMPLER_DDIM_REVERSE = 2        # x_t -> x_{t+1}, the deterministic DDIM step run upward (gaussian_diffusion.py:910-946); no noise term
+SAMPLER_PLMS = 3                # plms_sample (gaussian_diffusion.py:1084-1166): Pseudo Linear Multistep, orders 1..4; no noise term.
+                                # It carries a history, so it runs through sample_loop_plms / Schedule.plms_step, not sample_loop / step
 NOISE_BUFFER, NOISE_PHILOX = 0, 1
 
 # Largest classifier-free guidance factor (the larger of s and 1 - s per clip) at which the default f16-operand path was measured to
@@ -108,6 +110,48 @@ class Schedule:
                                              N.ptr(t), B, x.numel() // B, int(sampler), int(mean_type), float(eta), int(bool(mask_noise)),
                                              int(bool(clip_denoised)), N.ptr(sample), N.ptr(xstart), N.stream_ptr(dev)))
         return sample, xstart
+
+    def plms_step(self, model_output, x, t, history=(), order=None, mask=None, motion=None, clip_denoised=False, mean_type=0,
+                  first_half=False, eps_out=None):
+        """(sample, pred_xstart, eps) of one plms_sample multistep step given the model output (reference :1143-1166).
+        history: the earlier epsilons OLDEST FIRST, as the reference's `old_eps` list holds them; cur_order = min(order, 1 + len(history))
+        (order None: 1 + len(history)) and only the newest cur_order - 1 entries are read.  eps_out: where to write this step's eps (it may
+        be the oldest history entry: a ring).  first_half=True: the first half of the Euler step that opens a chain of order > 1 --
+        'sample' is then x_mid = pred sqrt(abar_prev) + sqrt(1 - abar_prev) eps and the history is not read."""
+        dev = x.device
+        mo = _f32c(model_output, dev, "model_output")
+        x = _f32c(x, dev, "x")
+        mask = None if mask is None else _f32c(mask, dev, "mask")
+        motion = None if motion is None else _f32c(motion, dev, "motion")
+        t = t.to(device=dev, dtype=torch.int64).contiguous()
+        hist = [_f32c(h, dev, "history") for h in history]
+        cur = 1 + len(hist) if order is None else min(int(order), 1 + len(hist))
+        if not first_half and not 1 <= cur <= 4:
+            raise ValueError("order is invalid (should be int from 1-4).")
+        e = [hist[-k] if k < cur and not first_half else None for k in (1, 2, 3)]
+        sample, xstart = torch.empty_like(x), torch.empty_like(x)
+        eps = torch.empty_like(x) if eps_out is None else eps_out
+        assert eps.is_contiguous() and eps.dtype == torch.float32 and eps.shape == x.shape
+        B = x.shape[0]
+        N.check(N.lib().mst_plms_epilogue(self.handle, N.ptr(mo), N.ptr(x), N.ptr(mask), N.ptr(motion), N.ptr(t), B, x.numel() // B,
+                                          int(mean_type), int(bool(clip_denoised)), cur, int(bool(first_half)), N.ptr(e[0]), N.ptr(e[1]),
+                                          N.ptr(e[2]), N.ptr(sample), N.ptr(xstart), N.ptr(eps), N.stream_ptr(dev)))
+        return sample, xstart, eps
+
+
+    def plms_euler(self, model_output, x_mid, x, eps, t, mask=None, motion=None, clip_denoised=False, mean_type=0):
+        """The second half of the Euler step (reference :1138-1141): `model_output` is the model at (x_mid, t - 1), `x` the chain's
+        original input, `eps` the first evaluation's; `t` the step's own indices (>= 1).  Returns the sample."""
+        dev = x.device
+        mo, x_mid, x, eps = (_f32c(v, dev, n) for v, n in ((model_output, "model_output"), (x_mid, "x_mid"), (x, "x"), (eps, "eps")))
+        mask = None if mask is None else _f32c(mask, dev, "mask")
+        motion = None if motion is None else _f32c(motion, dev, "motion")
+        t = t.to(device=dev, dtype=torch.int64).contiguous()
+        sample = torch.empty_like(x)
+        B = x.shape[0]
+        N.check(N.lib().mst_plms_euler(self.handle, N.ptr(mo), N.ptr(x_mid), N.ptr(x), N.ptr(eps), N.ptr(mask), N.ptr(motion), N.ptr(t), B,
+                                       x.numel() // B, int(mean_type), int(bool(clip_denoised)), N.ptr(sample), N.stream_ptr(dev)))
+        return sample
 
 
 def plan_style_segments(styles, S, tile_rows):
@@ -445,6 +489,47 @@ class DenoiserEngine:
             dump = torch.empty((nsteps,) + tuple(x.shape), dtype=torch.float32, device=self.device)
             a.xstart_dump_dev = dump.data_ptr()
         N.check(N.lib().mst_sample_loop(self.handle, schedule.handle, C.byref(a), N.stream_ptr(self.device)))
+        self._loop_keepalive = keep
+        return (x, dump) if dump_xstart else x
+
+    def sample_loop_plms(self, schedule, x, t_start, t_end=0, order=2, steps_done=0, hist=None, cfg=False, scale=None, mask=None,
+                         motion=None, clip_denoised=False, dump_xstart=False, noise=None, seed=None, eta=0.0, mask_noise=False):
+        """Run PLMS chain steps at indices t_start..t_end (descending) in place on `x`.  hist: the [3,B,F,1,T] float32 eps ring (chain
+        step k writes slot k % 3; required for order > 1), steps_done: chain steps taken by earlier calls with this ring (0 starts a
+        chain: for order > 1 its first step is the two-evaluation Euler step).  A k-step call equals k one-step calls with steps_done
+        carried forward, bit for bit.  Returns x (and the x0-hat dump, first evaluation of every step, when requested).
+        noise, seed, eta, mask_noise: handed to the library as given and ignored there (the step has no noise term)."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        if cfg:
+            self.check_guidance_scale(scale)
+        B, F, one, T = x.shape
+        nsteps = abs(t_start - t_end) + 1
+        a = N.MstLoopArgs()
+        a.batch, a.frames, a.cfg, a.sampler = B, T, int(bool(cfg)), SAMPLER_PLMS
+        a.clip_denoised = int(bool(clip_denoised))
+        a.t_start, a.t_end, a.eta, a.mask_noise = int(t_start), int(t_end), float(eta), int(bool(mask_noise))
+        a.noise_mode, a.seed = NOISE_PHILOX, int(seed or 0)
+        if noise is not None:
+            a.noise_mode, a.noise_dev = NOISE_BUFFER, noise.data_ptr()
+        pl = N.MstPlmsArgs()
+        pl.order, pl.steps_done = int(order), int(steps_done)
+        keep = [noise]
+        if hist is not None:
+            assert hist.is_cuda and hist.dtype == torch.float32 and hist.is_contiguous() and hist.numel() == 3 * x.numel(), \
+                "hist: a contiguous float32 [3,B,F,1,T] ring"
+            pl.hist_dev = hist.data_ptr()
+            keep.append(hist)
+        for name, val in (("scale_dev", scale), ("inpainting_mask_dev", mask), ("inpainted_motion_dev", motion)):
+            if val is not None:
+                val = _f32c(val, self.device, name)
+                keep.append(val)
+                setattr(a, name, val.data_ptr())
+        a.x_dev = x.data_ptr()
+        dump = None
+        if dump_xstart:
+            dump = torch.empty((nsteps,) + tuple(x.shape), dtype=torch.float32, device=self.device)
+            a.xstart_dump_dev = dump.data_ptr()
+        N.check(N.lib().mst_sample_loop_plms(self.handle, schedule.handle, C.byref(a), C.byref(pl), N.stream_ptr(self.device)))
         self._loop_keepalive = keep
         return (x, dump) if dump_xstart else x
 

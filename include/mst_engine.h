@@ -145,7 +145,10 @@ int mst_forward(mst_engine* e, const float* x_dev, const int64_t* t_dev, const f
  * t_start + 1, ..., t_end and leaves x at index t_end + 1.  eta must be 0 ("Reverse ODE only for deterministic path", :923).  The
  * step has no noise term: noise_mode, seed and mask_noise are ignored and noise_dev may be NULL.  alphas_cumprod_next[t] (:193) is
  * read as MST_TAB alphas_cumprod[t + 1], and 0 at t == n - 1: the schedule's table layout is unchanged. */
-enum { MST_SAMPLER_DDPM = 0, MST_SAMPLER_DDIM = 1, MST_SAMPLER_DDIM_REVERSE = 2 };
+/* MST_SAMPLER_PLMS: plms_sample (gaussian_diffusion.py:1084-1166), Pseudo Linear Multistep of order 1..4.  It carries a history of
+ * up to three earlier epsilons between steps, so it has an entry point of its own, mst_sample_loop_plms below: mst_sample_loop
+ * refuses this id by that name, and mst_step_backward refuses it (the reference has no `_with_grad` form of plms_sample). */
+enum { MST_SAMPLER_DDPM = 0, MST_SAMPLER_DDIM = 1, MST_SAMPLER_DDIM_REVERSE = 2, MST_SAMPLER_PLMS = 3 };
 enum { MST_NOISE_BUFFER = 0, MST_NOISE_PHILOX = 1 };
 
 typedef struct mst_loop_args {
@@ -168,6 +171,32 @@ typedef struct mst_loop_args {
 } mst_loop_args;
 
 int mst_sample_loop(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, void* stream);
+
+/* -----------------------------------------------------------------------------------------
+ * The PLMS sampler: plms_sample_loop (gaussian_diffusion.py:1168-1279) as native calls.
+ * A chain is the sequence of steps that share one history.  Step k of a chain (k = steps_done + the step's position in this call):
+ *   k == 0 and order > 1   the Pseudo Improved Euler step: TWO model evaluations, at (x, t) and at (x_mid, t - 1); run from the
+ *                          host as two model-output-only passes and two small elementwise kernels, once per chain;
+ *   otherwise              the multistep step with cur_order = min(order, k + 1), fused into the output projection like the other
+ *                          samplers' steps.  cur_order and the ring slots are read on the device, so one captured graph serves every
+ *                          order and every position in a chain.
+ * hist_dev is a ring of three fp32 slots [3][B,F,1,T] in caller-owned memory (B rows under CFG too, not 2B): chain step k writes its
+ * eps into slot k % 3 and reads the newest earlier ones from slots (k - 1) % 3, (k - 2) % 3, (k - 3) % 3.  (During the Euler step
+ * slot 1 holds the chain's original x.)  The history is eps, never eps' or the second evaluation's eps.  It may be NULL for order 1.
+ * The index range is descending as for MST_SAMPLER_DDIM.  a->sampler, eta, noise_mode, seed, noise_dev and mask_noise are ignored (the
+ * step has no noise term); noise_dev may be NULL.  xstart_dump_dev entry j is the x0-hat of the call's step j (first evaluation).
+ * A k-step call equals k one-step calls with steps_done carried forward, bit for bit (x and the ring).
+ * Refused, each by name: order outside 1..4; steps_done < 0; hist_dev NULL with order > 1; a chain that STARTS at index 0 with
+ * order > 1 -- the reference evaluates the model at t - 1 = -1 there, which silently wraps to the last table entry; this library
+ * refuses instead.
+ * ----------------------------------------------------------------------------------------- */
+typedef struct mst_plms_args {
+    int32_t order;                  /* 1..4                                                            */
+    int32_t steps_done;             /* chain steps taken by earlier calls; 0 starts a chain            */
+    float*  hist_dev;               /* [3][B,F,1,T] float32 eps ring (may be NULL when order == 1)     */
+} mst_plms_args;
+int mst_sample_loop_plms(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_plms_args* pl, void* stream);
+
 
 /* Number of independent clip slices (1..3) mst_sample_loop runs on separate streams for this
  * batch of `frames`-frame clips (frames <= 0: the engine's max_frames; the policy depends on the
@@ -209,6 +238,24 @@ int mst_step_epilogue_mt(const mst_schedule* s, const float* model_out_dev, cons
                          const int64_t* t_dev, int32_t batch, int64_t per_clip, int32_t sampler, int32_t mean_type,
                          float eta, int32_t mask_noise, int32_t clip_denoised,
                          float* sample_out_dev, float* xstart_out_dev, void* stream);
+
+/* plms_sample for callers that bring their own model (gaussian_diffusion.py:1084-1166), elementwise on [batch][per_clip] tensors.
+ *   mst_plms_epilogue   the multistep step: cur_order 1..4, e1 / e2 / e3 the history NEWEST FIRST (only cur_order - 1 are read, the
+ *                       rest may be NULL).  Outputs, any of which may be NULL: sample (t != 0 ? mean : pred), xstart (x0-hat, after
+ *                       blend / conversion / clip), eps_out (what the history takes).  eps_out may alias e3 and sample may alias x.
+ *                       first_half != 0: the first half of the Euler step that opens a chain instead -- sample is
+ *                       x_mid = pred sqrt(abar_prev) + sqrt(1 - abar_prev) eps (from pred itself); cur_order, e1..e3 are ignored.
+ *   mst_plms_euler      the second half: model_out is the model at (x_mid, t - 1), x the chain's original input, eps the first
+ *                       evaluation's; tables at t - 1 for eps2, at t for the update.  Every t must be >= 1.  sample may alias x_mid.
+ * mean_type as mst_step_epilogue_mt; mask / motion: the inpainting pair, both or neither. */
+int mst_plms_epilogue(const mst_schedule* s, const float* model_out_dev, const float* x_dev, const float* mask_dev, const float* motion_dev,
+                      const int64_t* t_dev, int32_t batch, int64_t per_clip, int32_t mean_type, int32_t clip_denoised, int32_t cur_order,
+                      int32_t first_half, const float* e1_dev, const float* e2_dev, const float* e3_dev, float* sample_out_dev,
+                      float* xstart_out_dev, float* eps_out_dev, void* stream);
+int mst_plms_euler(const mst_schedule* s, const float* model_out_dev, const float* x_mid_dev, const float* x_dev, const float* eps_dev,
+                   const float* mask_dev, const float* motion_dev, const int64_t* t_dev, int32_t batch, int64_t per_clip, int32_t mean_type,
+                   int32_t clip_denoised, float* sample_out_dev, void* stream);
+
 
 /* Standard-normal fill with the engine's Philox stream (the generator MST_NOISE_PHILOX uses
  * inside the fused step), so a caller can reproduce in-loop noise: element (clip, f, t) of step
