@@ -34,6 +34,11 @@ class MstPlmsArgs(C.Structure):
     _fields_ = [("order", C.c_int32), ("steps_done", C.c_int32), ("hist_dev", C.c_void_p)]
 
 
+class MstGuideArgs(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("follow_schedule", C.c_int32), ("grad_dev", C.c_void_p), ("target_dev", C.c_void_p),
+                ("mask_dev", C.c_void_p), ("weight_dev", C.c_void_p)]
+
+
 # name -> (restype, argtypes); must list every function include/mst_engine.h declares
 SIGNATURES = {
     "mst_last_error": (C.c_char_p, []),
@@ -46,12 +51,17 @@ SIGNATURES = {
     "mst_weights_complete": (C.c_int, [C.c_void_p]),
     "mst_schedule_create": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "mst_schedule_destroy": (None, [C.c_void_p]),
+    "mst_schedule_set_variance": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mst_set_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "mst_set_text_dropped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mst_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_void_p]),
     "mst_sample_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.c_void_p]),
     "mst_sample_loop_plms": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.POINTER(MstPlmsArgs), C.c_void_p]),
+    "mst_sample_loop_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.POINTER(MstGuideArgs), C.c_void_p]),
+    "mst_step_epilogue_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32,
+                                           C.POINTER(MstGuideArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mst_plms_epilogue": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

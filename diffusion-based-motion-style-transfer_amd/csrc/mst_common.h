@@ -306,8 +306,11 @@ __device__ __forceinline__ void philox_normal4(uint32_t tq, uint32_t f, uint32_t
 // The fused kernels' MODE (0 model output only, 1 ancestral, 2 DDIM, 3 DDIM reverse, 4 PLMS multistep) -> SAMPLER, and whether the step
 // has a noise term at all: MODEs 3 and 4 have none, so their instantiations contain no Philox draw, no noise load and no noise mask -- a
 // compile-time property, not sigma = 0 times a draw.
-constexpr int step_sampler(int mode) { return mode == 4 ? 3 : mode == 3 ? 2 : mode == 2 ? 1 : 0; }
-constexpr bool step_draws(int mode) { return mode == 1 || mode == 2; }
+// MODEs 5 and 6 are the GUIDED ancestral and DDIM steps (cond_fn: condition_mean :454-467, condition_score :484-506): the same
+// samplers with a gradient operand, step_update_guided below.  Instantiations of their own, so MODEs 1 and 2 compile to what they were.
+constexpr int step_sampler(int mode) { return mode == 6 ? 1 : mode == 5 ? 0 : mode == 4 ? 3 : mode == 3 ? 2 : mode == 2 ? 1 : 0; }
+constexpr bool step_draws(int mode) { return mode == 1 || mode == 2 || mode == 5 || mode == 6; }
+constexpr bool step_guided(int mode) { return mode == 5 || mode == 6; }
 struct StepCoef {   // per-clip scalars gathered from the float32 tables at index t
     float c1, c2, sigma_ddpm;      // posterior_mean_coef1/2, nonzero * exp(0.5 * logvar)
     float srac, srm1ac;            // sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod
@@ -398,6 +401,40 @@ __device__ __forceinline__ float step_update(const StepCoef& c, float model_out,
     }
 }
 
+// The guided step (cond_fn): g is grad log p(y | x_t) at this element, gcoef the step's scalar in front of it.
+//   SAMPLER 0, condition_mean (:463-467, called at :577-580 / inpainting_gaussian_diffusion.py:59-62): mean += variance_t g, with
+//     gcoef = p_mean_var["variance"] (posterior_variance[t] or the betas-based row -- NOT exp(log_variance): exactly 0 at index 0
+//     under FIXED_SMALL), then the noise term as in step_update.
+//   SAMPLER 1, condition_score (:494-505, called at :821-824 / igd:150-153), then :828-846: eps = (srac x - pred) / srm1ac;
+//     eps -= sqrt(1 - abar_t) g (gcoef); pred' = srac x - srm1ac eps; eps RE-DERIVED from pred'; sample = pred' sqrt(abar_prev) +
+//     dir eps'' + sigma noise.
+// *pred is the UNGUIDED x0-hat in both (the reference returns out_orig["pred_xstart"], :847 / igd:177; condition_mean changes the mean
+// only).  Blend, conversion, clip and the noise mask stand in front, exactly as in step_update.
+template <int SAMPLER, int MEAN = 0>
+__device__ __forceinline__ float step_update_guided(const StepCoef& c, float gcoef, float g, float model_out, float x, float noise,
+                                                    bool has_blend, float mask, float motion, bool mask_noise, bool clip, float* pred) {
+    static_assert(SAMPLER == 0 || SAMPLER == 1, "ddim_reverse_sample and plms_sample take no cond_fn");
+    float out = model_out;
+    if (has_blend) out = out * (1.0f - mask) + motion * mask;
+    const float raw = out;
+    if (MEAN == 1) out = c.srac * x - c.srm1ac * out;
+    if (MEAN == 2) out = (1.0f / c.c1) * out - (c.c2 / c.c1) * x;
+    if (clip) out = fminf(fmaxf(out, -1.0f), 1.0f);
+    *pred = out;
+    if (mask_noise) noise = noise * (1.0f - mask);
+    if (SAMPLER == 0) {
+        float mean = MEAN == 2 ? raw : c.c1 * out + c.c2 * x;
+        mean = mean + gcoef * g;
+        return mean + c.sigma_ddpm * noise;
+    } else {
+        float eps = (c.srac * x - out) / c.srm1ac;
+        eps = eps - gcoef * g;
+        const float pp = c.srac * x - c.srm1ac * eps;
+        const float eps2 = (c.srac * x - pp) / c.srm1ac;
+        return pp * c.sq_abp + c.dir * eps2 + c.sigma_ddim * noise;
+    }
+}
+
 // The model output -> x0-hat of every sampler (blend on the RAW output, conversion, clip), as the first lines of step_update.
 template <int MEAN>
 __device__ __forceinline__ float step_pred(const StepCoef& c, float model_out, float x, bool has_blend, float mask, float motion, bool clip) {
@@ -458,6 +495,10 @@ struct LoopDev {
     // PLMS (read by the MODE 4 step kernels alone, plms_resolve): the fp32 eps ring [3][B,F,1,T] (slot stride `hist_stride` elements),
     // the sampler's order and the chain steps taken before this call -- step j of the call is chain step k = steps_done + j
     float* hist; unsigned long long hist_stride; int order; int steps_done;
+    // Guide (read by the MODE 5 / 6 step kernels alone, guide_resolve): kind (MST_GUIDE_*), the caller's gradient for this one step or the
+    // target guide's loop-constant operands (target y and mask m [B,F,1,T], weight w [B]; m may be null), whether the target follows the
+    // schedule, and the schedule's variance row [n] (condition_mean's p_mean_var["variance"]; no row of MST_TAB_*)
+    int g_kind; int g_follow; const float* g_grad; const float* g_target; const float* g_mask; const float* g_weight; const float* g_var;
 };
 
 // arguments of the fused diffusion step (output-projection epilogue)
@@ -516,6 +557,53 @@ __device__ __forceinline__ PlmsStep plms_resolve(const StepArgs& sa) {
     p.e2 = h + (size_t)((k + 1) % 3) * d.hist_stride;
     p.e3 = p.ew;
     return p;
+}
+
+// What a guided step reads besides StepCoef.  kind 1 (MST_GUIDE_GRADIENT): g = grad[idx].  kind 2 (MST_GUIDE_TARGET):
+// g = w[clip] m (a_t y - x_t), a_t = 1 or sqrt(abar_t) (row TAB_SQRT_AC) when the target follows the schedule -- the gradient of a
+// Gaussian log-likelihood around a_t y, computed here from x_t, which the step has loaded anyway.  Tensors are addressed like x; w
+// starts at the slice's first clip, so `clip` is the slice-local one.  gcoef: see step_update_guided.
+constexpr int GUIDE_GRADIENT = 1, GUIDE_TARGET = 2;
+struct GuideStep { int kind; const float *grad, *y, *m, *w; float a_t, gcoef; };
+template <int SAMPLER>
+__device__ __forceinline__ float guide_coef(const float* __restrict__ tab, const float* __restrict__ var, int nsteps, int t) {
+    if constexpr (SAMPLER == 0) return var[t];
+    else return sqrtf(1.0f - tab[TAB_AC * nsteps + t]);
+}
+__device__ __forceinline__ float guide_at(const float* __restrict__ tab, int nsteps, int t, int follow) {
+    return follow ? tab[TAB_SQRT_AC * nsteps + t] : 1.0f;
+}
+template <int SAMPLER>
+__device__ __forceinline__ GuideStep guide_resolve(const StepArgs& sa) {
+    const LoopDev& d = *sa.ld;
+    GuideStep g;
+    g.kind = d.g_kind;
+    g.grad = d.g_grad ? d.g_grad + sa.eo : nullptr;
+    g.y = d.g_target ? d.g_target + sa.eo : nullptr;
+    g.m = d.g_mask ? d.g_mask + sa.eo : nullptr;
+    g.w = d.g_weight ? d.g_weight + sa.clip0 : nullptr;
+    g.a_t = guide_at(sa.tab, sa.nsteps, sa.t, d.g_follow);
+    g.gcoef = guide_coef<SAMPLER>(sa.tab, d.g_var, sa.nsteps, sa.t);
+    return g;
+}
+__device__ __forceinline__ float guide_target(float w, bool has_m, float m, float a_t, float y, float x) {
+    const float d = a_t * y - x;
+    return has_m ? (w * m) * d : w * d;
+}
+// one element / four consecutive frames of the gradient (x: x_t there)
+__device__ __forceinline__ float guide_grad(const GuideStep& g, size_t idx, int clip, float x) {
+    if (g.kind == GUIDE_GRADIENT) return g.grad[idx];
+    return guide_target(g.w[clip], g.m != nullptr, g.m ? g.m[idx] : 0.f, g.a_t, g.y[idx], x);
+}
+__device__ __forceinline__ f32x4 guide_grad4(const GuideStep& g, size_t idx, int clip, const f32x4& x) {
+    if (g.kind == GUIDE_GRADIENT) return *reinterpret_cast<const f32x4*>(g.grad + idx);
+    const f32x4 y = *reinterpret_cast<const f32x4*>(g.y + idx);
+    f32x4 m = {0.f, 0.f, 0.f, 0.f}, r;
+    if (g.m) m = *reinterpret_cast<const f32x4*>(g.m + idx);
+    const float w = g.w[clip];
+#pragma unroll
+    for (int j = 0; j < 4; j++) r[j] = guide_target(w, g.m != nullptr, m[j], g.a_t, y[j], x[j]);
+    return r;
 }
 
 namespace mst {

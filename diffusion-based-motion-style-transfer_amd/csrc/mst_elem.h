@@ -213,6 +213,36 @@ __global__ void k_step_epilogue(const float* __restrict__ tab, int nsteps, float
     }
 }
 
+// The guided K10 / K10' stand-alone (p_sample / ddim_sample with a cond_fn, gaussian_diffusion.py:577-580 / :821-824, model output
+// produced elsewhere): step_update_guided with the gradient read (kind 1) or computed from the target guide's operands (kind 2).
+// var: the schedule's variance row (SAMPLER 0 only).  xstart is the UNGUIDED x0-hat.
+template <int SAMPLER, int MEAN>
+__global__ void k_step_epilogue_guided(const float* __restrict__ tab, const float* __restrict__ var, int nsteps, float eta,
+                                       const float* __restrict__ model_out, const float* __restrict__ x,
+                                       const float* __restrict__ noise, const float* __restrict__ mask,
+                                       const float* __restrict__ motion, const long long* __restrict__ t,
+                                       long long per_clip, int mask_noise, int clip_denoised, int kind, const float* __restrict__ grad,
+                                       const float* __restrict__ target, const float* __restrict__ gmask, const float* __restrict__ weight,
+                                       int follow, float* __restrict__ sample, float* __restrict__ xstart) {
+    const int clip = blockIdx.y;
+    const int ti = (int)t[clip];
+    const StepCoef sc = step_coef_for<SAMPLER>(tab, nsteps, ti, eta);
+    const GuideStep gs{kind, grad, target, gmask, weight, guide_at(tab, nsteps, ti, follow), guide_coef<SAMPLER>(tab, var, nsteps, ti)};
+    const bool blend = mask != nullptr && motion != nullptr;
+    const size_t base = (size_t)clip * per_clip;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < per_clip; i += (long long)gridDim.x * blockDim.x) {
+        size_t idx = base + i;
+        float m = mask ? mask[idx] : 0.f;
+        float mot = blend ? motion[idx] : 0.f;
+        const float xi = x[idx];
+        float pred;
+        float nx = step_update_guided<SAMPLER, MEAN>(sc, gs.gcoef, guide_grad(gs, idx, clip, xi), model_out[idx], xi, noise ? noise[idx] : 0.f,
+                                                     blend, m, mot, mask_noise && mask, clip_denoised, &pred);
+        if (sample) sample[idx] = nx;
+        if (xstart) xstart[idx] = pred;
+    }
+}
+
 // plms_sample stand-alone (gaussian_diffusion.py:1084-1166; model output produced elsewhere): the multistep step, cur_order 1..4
 // with the history newest first (e1, e2, e3; only cur_order - 1 of them are read), or -- cur_order 0 -- the first half of the Euler
 // step that opens a chain (sample = x_mid).  t: per-clip indices, or null and `t_uniform` for every clip (the native loop's warm-up).

@@ -96,6 +96,8 @@ __device__ __forceinline__ void emb_stream(const char* wsrc, unsigned w_voff, Be
 // MODE 3 (the reverse step) has no noise term: noise1() is never called, load() reads no noise buffer, `nz` is never touched.
 // MODE 4 (the PLMS multistep step) has none either; its eps history is NOT held across the GEMM (up to three more f32x4 per item): apply()
 // loads the entries the step's cur_order needs item by item, in front of the item's tile read, and stores the item's eps into the ring.
+// MODEs 5 / 6 (the guided steps) draw and load like MODEs 1 / 2; the gradient operands (one fp32 tensor for a caller's gradient, the
+// target and its mask for the target guide) are loaded in apply(), item by item, like the PLMS history.
 template <int MODE, int NU>
 struct OutItems {
     f32x4 nz[NU], xv[NU], mk1, mot1;          // (mk1, mot1): mask / motion of the thread's FIRST item that needs them, prefetched (item u1)
@@ -168,6 +170,8 @@ struct OutItems {
         float* trow = tile + f0 * LDT + (threadIdx.x % TG) * 4;
         PlmsStep ps{};
         if constexpr (MODE == 4) ps = plms_resolve(sa);
+        GuideStep gd{};
+        if constexpr (step_guided(MODE)) gd = guide_resolve<step_sampler(MODE)>(sa);
 #pragma unroll
         for (int u = 0; u < NU; u++) {
             if (u >= nvalid) continue;
@@ -198,6 +202,21 @@ struct OutItems {
                 gstore(sa.sample + idx, nx);
                 if (sa.xstart) gstore(sa.xstart + idx, pred);
                 if (ps.ew) gstore(ps.ew + idx, ep);
+                if (epi.xt_next) *reinterpret_cast<f32x4*>(trow + 32 * u * LDT) = nx;
+                continue;
+            }
+            if constexpr (step_guided(MODE)) {
+                const f32x4 g4 = guide_grad4(gd, idx, clip, xv[u]);
+                const f32x4 acc4 = *reinterpret_cast<const f32x4*>(trow + 32 * u * LDT);
+                const bool bl = blend && !(use_mask && rf[u] == 0), mn = sa.mask_noise && use_mask && rf[u] != 0;      // (an all-zero mask row: blend and noise mask are the identity)
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    float p;
+                    nx[j] = step_update_guided<step_sampler(MODE)>(sc, gd.gcoef, g4[j], acc4[j] + bu[u], xv[u][j], nz[u][j], bl, mk[j], mot[j], mn, sa.clip, &p);
+                    pred[j] = p;
+                }
+                gstore(sa.sample + idx, nx);
+                if (sa.xstart) gstore(sa.xstart + idx, pred);
                 if (epi.xt_next) *reinterpret_cast<f32x4*>(trow + 32 * u * LDT) = nx;
                 continue;
             }

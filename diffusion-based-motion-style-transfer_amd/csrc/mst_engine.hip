@@ -122,6 +122,7 @@ struct mst_schedule {
     int n = 0, device = 0;
     float* tab = nullptr;          // [NTAB][n] float32
     long long* tmap = nullptr;     // [n] int64 original-process timesteps
+    float* var = nullptr;          // [n] float32 variance row (mst_schedule_set_variance; read by the guided ancestral step alone)
 };
 
 struct LayerW {
@@ -312,8 +313,17 @@ extern "C" int mst_schedule_create(int32_t num_steps, const float* tables_host, 
     return 0;
 }
 
+extern "C" int mst_schedule_set_variance(mst_schedule* s, const float* variance_host) {
+    if (!s || !variance_host) return fail("mst_schedule_set_variance: null argument");
+    ON_DEVICE(s->device);
+    if (!s->var) HIPCHECK(hipMalloc((void**)&s->var, sizeof(float) * s->n));
+    HIPCHECK(hipMemcpy(s->var, variance_host, sizeof(float) * s->n, hipMemcpyHostToDevice));
+    return 0;
+}
+
 extern "C" void mst_schedule_destroy(mst_schedule* s) {
     if (!s) return;
+    (void)hipFree(s->var);
     (void)hipFree(s->tab);
     (void)hipFree(s->tmap);
     delete s;
@@ -1802,6 +1812,7 @@ extern "C" int mst_loop_slices(const mst_engine* e, int32_t batch, int32_t cfg, 
 struct LoopPlan {
     const mst_schedule* s; const mst_loop_args* a; int nsl; size_t per_clip, clip_elems;
     hipStream_t streams[mst_engine::MAX_SLICES];
+    const mst_guide_args* gd = nullptr;      // mst_sample_loop_guided: the step kernels are the guided MODEs
 };
 // frames_ready / frames_next: the step's frame rows (ws.xt) were written by the previous step's epilogue / this step's epilogue
 // writes them for the next one (mst_sample_loop decides; see DEpiEmbedOut::xt_next)
@@ -1848,7 +1859,9 @@ static int enqueue_step(mst_engine* e, const LoopPlan& p, int joff, int nsj, boo
         sa.eo = eo;
         sa.step_stride = p.clip_elems;
         sa.rowflag = (a->inpainting_mask_dev && a->inpainted_motion_dev) ? e->rowflag + (size_t)c0 * e->cfg.feats : nullptr;
-        if (a->sampler == MST_SAMPLER_DDPM) CHECK(launch_out_nt<1>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
+        if (p.gd && a->sampler == MST_SAMPLER_DDPM) CHECK(launch_out_nt<5>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
+        else if (p.gd) CHECK(launch_out_nt<6>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
+        else if (a->sampler == MST_SAMPLER_DDPM) CHECK(launch_out_nt<1>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
         else if (a->sampler == MST_SAMPLER_DDIM_REVERSE) CHECK(launch_out_nt<3>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
         else if (a->sampler == MST_SAMPLER_PLMS) CHECK(launch_out_nt<4>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
         else CHECK(launch_out_nt<2>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
@@ -1919,7 +1932,9 @@ static int join_slices(mst_engine* e, const LoopPlan& p) {
 // tensors and its step index through the LoopDev block in device memory, which a one-thread kernel at the end of the graph
 // advances, so the instantiated graph is reused by every replay and by every later call with the same shapes.
 // pl: the PLMS chain state (mst_sample_loop_plms; a->sampler is then MST_SAMPLER_PLMS), null for every other sampler.
-static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_plms_args* pl, void* stream) {
+// gd: the guide (mst_sample_loop_guided, which has checked it; MST_SAMPLER_DDPM / MST_SAMPLER_DDIM only), null for an unguided loop.
+static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_plms_args* pl, void* stream,
+                           const mst_guide_args* gd = nullptr) {
     if (!s || !a) return fail("mst_sample_loop: null argument");
     CHECK(check_ready(e, a->batch, a->frames, a->cfg));
     if (a->sampler == MST_SAMPLER_PLMS && !pl)
@@ -1961,6 +1976,7 @@ static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_
     // flat in the block count at this size).  CFG batches are sliced the same way (cond + uncond twins stay together).
     LoopPlan p{s, a, loop_slices_for(e, a->batch, a->cfg, a->frames), (size_t)e->cfg.feats * a->frames, (size_t)a->batch * e->cfg.feats * a->frames,
                {st, e->aux_stream[0], e->aux_stream[1], e->aux_stream[2], e->aux_stream[3], e->aux_stream[4], e->aux_stream[5], e->aux_stream[6]}};
+    p.gd = gd;
     if (styles_on(e)) CHECK(style_plan(e, a->batch, a->cfg, a->frames, p.nsl, st));     // before the fork: every slice stream is behind it
     // per-call arguments -> device (pinned staging slot; the slot's previous upload has long completed when it comes round again)
     {
@@ -1970,7 +1986,9 @@ static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_
         LoopDev& h = e->ld_pin[slot];
         h = LoopDev{a->x_dev, a->inpainting_mask_dev, a->inpainted_motion_dev, a->noise_dev, a->scale_dev, a->xstart_dump_dev,
                     a->seed, a->eta, a->t_start, trows, 0, up ? 1 : 0,
-                    pl ? pl->hist_dev : nullptr, (unsigned long long)p.clip_elems, pl ? pl->order : 0, pl ? pl->steps_done : 0};
+                    pl ? pl->hist_dev : nullptr, (unsigned long long)p.clip_elems, pl ? pl->order : 0, pl ? pl->steps_done : 0,
+                    gd ? gd->kind : 0, gd ? gd->follow_schedule : 0, gd ? gd->grad_dev : nullptr, gd ? gd->target_dev : nullptr,
+                    gd ? gd->mask_dev : nullptr, gd ? gd->weight_dev : nullptr, s->var};
         HIPCHECK(hipMemcpyAsync(e->ld_dev, &h, sizeof(LoopDev), hipMemcpyHostToDevice, st));
         HIPCHECK(hipEventRecord(e->ld_ev[slot], st));
     }
@@ -1984,7 +2002,8 @@ static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_
     std::vector<long long> key = {a->batch, a->frames, a->cfg, a->sampler, a->noise_mode, a->mask_noise, a->clip_denoised,
                                   a->inpainting_mask_dev != nullptr, a->inpainted_motion_dev != nullptr, a->xstart_dump_dev != nullptr,
                                   a->scale_dev != nullptr, p.nsl, U, (long long)(size_t)s->tab, s->n, e->small_m, e->fuse_tail,
-                                  e->fuse_qkv_attn, e->ln128_min_m, e->precise, e->tail_ntb, e->embed_fast, e->small_fast, e->small_ln};      // every switch run_trunk / loop_slices_for branch on
+                                  e->fuse_qkv_attn, e->ln128_min_m, e->precise, e->tail_ntb, e->embed_fast, e->small_fast, e->small_ln,
+                                  gd != nullptr};      // every switch run_trunk / loop_slices_for / enqueue_step branch on
     const int j0 = warm ? 1 : 0;                              // the warm-up is the call's step 0
     const bool use_graph = e->graph_on && !e->prof_on && e->dbg_stage < 0 && nrun - j0 >= 2 * U;
     bool forked = false;
@@ -2090,6 +2109,33 @@ extern "C" int mst_sample_loop_plms(mst_engine* e, const mst_schedule* s, const 
     return sample_loop_run(e, s, &b, pl, stream);
 }
 
+static_assert(MST_GUIDE_GRADIENT == GUIDE_GRADIENT && MST_GUIDE_TARGET == GUIDE_TARGET, "the kernels' guide kinds are the ABI's");
+static int guide_check(const char* who, const mst_schedule* s, int sampler, const mst_guide_args* g) {
+    if (sampler == MST_SAMPLER_DDIM_REVERSE)
+        return fail("%s: MST_SAMPLER_DDIM_REVERSE takes no guide: the reference's ddim_reverse_sample has no cond_fn", who);
+    if (sampler == MST_SAMPLER_PLMS) return fail("%s: MST_SAMPLER_PLMS takes no guide: guided PLMS is not built", who);
+    if (sampler != MST_SAMPLER_DDPM && sampler != MST_SAMPLER_DDIM) return fail("%s: bad sampler %d", who, sampler);
+    if (g->kind == MST_GUIDE_GRADIENT) {
+        if (!g->grad_dev) return fail("%s: MST_GUIDE_GRADIENT needs grad_dev (NULL)", who);
+    } else if (g->kind == MST_GUIDE_TARGET) {
+        if (!g->target_dev) return fail("%s: MST_GUIDE_TARGET needs target_dev (NULL)", who);
+        if (!g->weight_dev) return fail("%s: MST_GUIDE_TARGET needs weight_dev (NULL)", who);
+    } else
+        return fail("%s: bad guide kind %d (MST_GUIDE_GRADIENT = 1, MST_GUIDE_TARGET = 2)", who, g->kind);
+    if (sampler == MST_SAMPLER_DDPM && !s->var)
+        return fail("%s: a guided MST_SAMPLER_DDPM step needs the schedule's variance row: call mst_schedule_set_variance", who);
+    return 0;
+}
+
+// p_sample_loop / ddim_sample_loop with a cond_fn (gaussian_diffusion.py:644-794 / :948-1082 with :577-580 / :821-824).
+extern "C" int mst_sample_loop_guided(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_guide_args* g, void* stream) {
+    if (!s || !a || !g) return fail("mst_sample_loop_guided: null argument");
+    CHECK(guide_check("mst_sample_loop_guided", s, a->sampler, g));
+    if (g->kind == MST_GUIDE_GRADIENT && a->t_start != a->t_end)
+        return fail("mst_sample_loop_guided: MST_GUIDE_GRADIENT carries the gradient of ONE step: t_start %d must equal t_end %d", a->t_start, a->t_end);
+    return sample_loop_run(e, s, a, nullptr, stream, g);
+}
+
 // ------------------------------------------------------------------------------------------ elementwise ABI
 extern "C" int mst_q_sample(const mst_schedule* s, const float* x0, const float* noise, const float* mask, const int64_t* t,
                             int32_t batch, int64_t per_clip, float* out, void* stream) {
@@ -2135,6 +2181,32 @@ extern "C" int mst_step_epilogue(const mst_schedule* s, const float* model_out, 
                                  float* xstart, void* stream) {
     return mst_step_epilogue_mt(s, model_out, x, noise, mask, motion, t, batch, per_clip, sampler, 0, eta, mask_noise, clip_denoised, sample,
                                 xstart, stream);
+}
+
+// p_sample / ddim_sample with a cond_fn given the model output (gaussian_diffusion.py:577-580 / :821-846).
+extern "C" int mst_step_epilogue_guided(const mst_schedule* s, const float* model_out, const float* x, const float* noise,
+                                        const float* mask, const float* motion, const int64_t* t, int32_t batch, int64_t per_clip,
+                                        int32_t sampler, int32_t mean_type, float eta, int32_t mask_noise, int32_t clip_denoised,
+                                        const mst_guide_args* g, float* sample, float* xstart, void* stream) {
+    if (!s || !model_out || !x || !t || !g || batch < 1 || per_clip < 1) return fail("mst_step_epilogue_guided: bad arguments");
+    CHECK(guide_check("mst_step_epilogue_guided", s, sampler, g));
+    if (mean_type < 0 || mean_type > 2) return fail("mst_step_epilogue_guided: bad mean type %d (0 = x_start, 1 = epsilon, 2 = previous x)", mean_type);
+    ON_DEVICE(s->device);
+    int gx = (int)((per_clip + 255) / 256);
+    if (gx > 2048) gx = 2048;
+#define GSTEP_LAUNCH(S_, M_)                                                                                                             \
+    hipLaunchKernelGGL((k_step_epilogue_guided<S_, M_>), dim3(gx, batch), dim3(256), 0, (hipStream_t)stream, s->tab, s->var, s->n, eta,  \
+                       model_out, x, noise, mask, motion, (const long long*)t, (long long)per_clip, mask_noise, clip_denoised, g->kind,   \
+                       g->grad_dev, g->target_dev, g->mask_dev, g->weight_dev, g->follow_schedule, sample, xstart)
+    const bool ddim = sampler == MST_SAMPLER_DDIM;
+    switch (mean_type) {
+        case 0: if (ddim) GSTEP_LAUNCH(1, 0); else GSTEP_LAUNCH(0, 0); break;
+        case 1: if (ddim) GSTEP_LAUNCH(1, 1); else GSTEP_LAUNCH(0, 1); break;
+        default: if (ddim) GSTEP_LAUNCH(1, 2); else GSTEP_LAUNCH(0, 2); break;
+    }
+#undef GSTEP_LAUNCH
+    HIPCHECK(hipGetLastError());
+    return 0;
 }
 
 // plms_sample given the model output (gaussian_diffusion.py:1084-1166).  first_half: the first half of the Euler step instead.

@@ -590,7 +590,8 @@ struct DEpiEmbedIn {
 // straight from the accumulator layout, all work in 4-5 of the 8 waves: 36 us even at batch 16.)
 // MODE 0 model output only, 1 ancestral step, 2 DDIM step, 3 DDIM reverse step (x_t -> x_{t+1}: no noise term, so no draw, no noise
 // load and no noise mask in its instantiations), 4 PLMS multistep step (plms_update: no noise term either; cur_order and the eps ring
-// come from the loop block at run time, plms_resolve); NX = 2 is the CFG doubled batch.
+// come from the loop block at run time, plms_resolve), 5 / 6 the guided ancestral / DDIM step (step_update_guided; the guide's
+// operands come from the loop block, guide_resolve); NX = 2 is the CFG doubled batch.
 template <int MODE>
 struct DEpiEmbedOut {
     const float* bias; int F, T, total; float* out; StepArgs sa;
@@ -600,7 +601,7 @@ struct DEpiEmbedOut {
     __device__ __forceinline__ int rows() const { return total; }
     template <int BT, int BF> static constexpr int smem_bytes() { return BF * (BT + 4) * 4; }
 
-    __device__ __forceinline__ void one(const StepArgs& sa, const StepCoef& sc, float mo, size_t idx, float nz, bool blend, bool use_mask) const {
+    __device__ __forceinline__ void one(const StepArgs& sa, const StepCoef& sc, float mo, size_t idx, float nz, bool blend, bool use_mask, int clip = 0) const {
         if (MODE == 0) { out[idx] = mo; return; }
         const float mk = use_mask ? sa.mask[idx] : 0.f, mot = blend ? sa.motion[idx] : 0.f;
         float pred;
@@ -612,6 +613,15 @@ struct DEpiEmbedOut {
             sa.sample[idx] = nx;
             if (sa.xstart) sa.xstart[idx] = pred;
             if (ps.ew) ps.ew[idx] = e;
+            return;
+        }
+        if constexpr (step_guided(MODE)) {                     // the guided step, element-wise
+            const GuideStep gd = guide_resolve<step_sampler(MODE)>(sa);
+            const float xi = sa.x[idx];
+            const float nx = step_update_guided<step_sampler(MODE)>(sc, gd.gcoef, guide_grad(gd, idx, clip, xi), mo, xi, nz, blend, mk, mot,
+                                                                    sa.mask_noise && use_mask, sa.clip, &pred);
+            sa.sample[idx] = nx;
+            if (sa.xstart) sa.xstart[idx] = pred;
             return;
         }
         const float nx = step_update<step_sampler(MODE)>(sc, mo, sa.x[idx], nz, blend, mk, mot, sa.mask_noise && use_mask, sa.clip, &pred);
@@ -658,6 +668,8 @@ struct DEpiEmbedOut {
         constexpr int TG = BT / 4;
         PlmsStep ps{};
         if constexpr (MODE == 4) ps = plms_resolve(sa);
+        GuideStep gd{};
+        if constexpr (step_guided(MODE)) gd = guide_resolve<step_sampler(MODE)>(sa);
         if (vec && MODE != 0) {
             // Three items per thread and pass, loads first: one item at a time the loop is a chain of dependent global loads (x, the row
             // flag, then mask / motion) per iteration, nine iterations deep at F = 263 -- latency, not bandwidth.
@@ -724,6 +736,14 @@ struct DEpiEmbedOut {
                             ep[j] = e;
                         }
                         if (ps.ew) *reinterpret_cast<f32x4*>(ps.ew + idx[u]) = ep;
+                    } else if constexpr (step_guided(MODE)) {
+                        const f32x4 g4 = guide_grad4(gd, idx[u], clipu[u], xv[u]);
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            float p;
+                            nx[j] = step_update_guided<step_sampler(MODE)>(sc, gd.gcoef, g4[j], mo[j], xv[u][j], nz[u][j], blend, mk[u][j], mot[u][j], sa.mask_noise && use_mask, sa.clip, &p);
+                            pred[j] = p;
+                        }
                     } else {
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
@@ -764,7 +784,7 @@ struct DEpiEmbedOut {
                         philox_normal4((unsigned)(t >> 2), (unsigned)f, (unsigned)clip + sa.clip0, sa.step, sa.seed, nrm);
                         nz = nrm[t & 3];
                     }
-                    one(sa, sc, acc4[j] + b, idx, nz, blend, use_mask);
+                    one(sa, sc, acc4[j] + b, idx, nz, blend, use_mask, clip);
                 }
             }
         }

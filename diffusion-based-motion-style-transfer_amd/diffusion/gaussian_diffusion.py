@@ -175,7 +175,8 @@ class GaussianDiffusion:
         key = (device.index or 0, self.model_var_type)
         if key not in self._schedules:
             tmap = getattr(self, "timestep_map", None) or self._identity_map()
-            self._schedules[key] = _eng.Schedule(self, tmap, device, log_variance=self._variance_tables()[1])
+            var, logvar = self._variance_tables()
+            self._schedules[key] = _eng.Schedule(self, tmap, device, log_variance=logvar, variance=var)
         return self._schedules[key]
 
     @staticmethod
@@ -286,11 +287,42 @@ class GaussianDiffusion:
             noise = noise[[0]].repeat(x.shape[0], 1, 1, 1)
         return noise
 
+    # ------------------------------------------------------------------------------ guidance (cond_fn)
+    def _wrap_cond(self, cond_fn):
+        return cond_fn          # (SpacedDiffusion: the cond_fn sees timestep_map[t], respace.py:104-108)
+
+    def _cond_gradient(self, cond_fn, x, t, model_kwargs):
+        """grad log p(y | x_t) as the reference asks for it (:463 / :497): cond_fn(x, scaled t, **model_kwargs).  It does not depend on
+        the model output, so it is evaluated in front of the step and handed to the step kernel as a tensor (MST_GUIDE_GRADIENT)."""
+        with th.no_grad():
+            g = self._wrap_cond(cond_fn)(x, self._scale_timesteps(t), **(model_kwargs or {}))
+        assert g.shape == x.shape, "cond_fn must return a gradient of x's shape"
+        return g.float()
+
+    def condition_mean(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """mean + variance * cond_fn(x, t) (reference :454-467; Sohl-Dickstein et al. 2015), torch ops on any device.  The samplers
+        below do the same inside the step kernel (step_update_guided)."""
+        gradient = self._cond_gradient(cond_fn, x, t, model_kwargs)
+        return p_mean_var["mean"].float() + p_mean_var["variance"] * gradient
+
+    def condition_score(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """p_mean_var with the score conditioned by cond_fn (reference :484-506; Song et al. 2020), torch ops on any device."""
+        alpha_bar = _extract_into_tensor(self.alphas_cumprod, t, x.shape)
+        eps = self._predict_eps_from_xstart(x, t, p_mean_var["pred_xstart"])
+        eps = eps - (1 - alpha_bar).sqrt() * self._cond_gradient(cond_fn, x, t, model_kwargs)
+        out = p_mean_var.copy()
+        out["pred_xstart"] = self._predict_xstart_from_eps(x, t, eps)
+        out["mean"], _, _ = self.q_posterior_mean_variance(x_start=out["pred_xstart"], x_t=x, t=t)
+        return out
+
     def _fused_step(self, sampler, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, const_noise, eta=0.0):
-        if cond_fn is not None or denoised_fn is not None:
-            raise NotImplementedError("cond_fn / denoised_fn are never set by this code base (SURVEY.md section 9)")
+        if sampler == _eng.SAMPLER_DDIM_REVERSE and (cond_fn is not None or denoised_fn is not None):
+            raise NotImplementedError("ddim_reverse_sample: cond_fn / denoised_fn are not built for the reverse step (the reference's "
+                                      "signature has no cond_fn, :910-919); p_sample and ddim_sample take them")
         with th.no_grad():
             out = self._model_output(model, x, t, model_kwargs)
+        if cond_fn is not None or denoised_fn is not None:
+            return self._guided_step(sampler, out, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, const_noise, eta)
         # (the reverse step has no noise term: nothing is drawn, so the caller's generator is left where it was)
         reverse = sampler == _eng.SAMPLER_DDIM_REVERSE
         noise = None if reverse else self._draw(x, const_noise)
@@ -302,6 +334,37 @@ class GaussianDiffusion:
         sample, pred = self._schedule(x.device).step(
             out, x, t, noise, sampler, eta, mask=mask if mask is not None else nmask, motion=motion,
             mask_noise=nmask is not None, clip_denoised=clip_denoised, mean_type=mean_type)
+        return {"sample": sample, "pred_xstart": pred}
+
+    def _guided_step(self, sampler, out, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, const_noise, eta):
+        """p_sample / ddim_sample with a cond_fn and / or a denoised_fn, behind the model output `out`.
+        cond_fn: its gradient first, then the guided step kernel (mst_step_epilogue_guided, MST_GUIDE_GRADIENT).
+        denoised_fn (reference :389-396, inside process_xstart): host composition -- the inpainting blend and the x0-hat conversion
+        in torch (:341-349, :398-412), denoised_fn, then the step kernel on the result as an x_start prediction without a blend;
+        clamp, noise mask and the guide stay in the kernel."""
+        mask, motion = self._inpaint_pair(model_kwargs)
+        nmask = self._noise_mask(model_kwargs)
+        mean_type = {ModelMeanType.START_X: 0, ModelMeanType.EPSILON: 1, ModelMeanType.PREVIOUS_X: 2}[self.model_mean_type]
+        grad = None if cond_fn is None else self._cond_gradient(cond_fn, x, t, model_kwargs)
+        if denoised_fn is not None:
+            if self.model_mean_type == ModelMeanType.PREVIOUS_X:
+                raise NotImplementedError("denoised_fn with a previous-x model: the posterior mean is the raw model output there "
+                                          "(:399-403), which the x_start form of the step kernel cannot carry")
+            with th.no_grad():
+                if mask is not None:
+                    assert out.shape == mask.shape == motion.shape
+                    m = th.ones_like(mask, dtype=th.float) * mask
+                    out = out * (1 - m) + motion * m
+                out = denoised_fn(self._xstart_from_output(out, x, t))
+            mask, motion, mean_type = None, None, 0
+        noise = self._draw(x, const_noise)
+        sch = self._schedule(x.device)
+        kw = dict(mask=mask if mask is not None else nmask, motion=motion, mask_noise=nmask is not None,
+                  clip_denoised=clip_denoised, mean_type=mean_type)
+        if grad is None:
+            sample, pred = sch.step(out, x, t, noise, sampler, eta, **kw)
+        else:
+            sample, pred = sch.step_guided(out, x, t, noise, _eng.guide_args(x, grad=grad), sampler, eta, **kw)
         return {"sample": sample, "pred_xstart": pred}
 
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
@@ -380,8 +443,23 @@ class GaussianDiffusion:
             img = self.q_sample(init_image, my_t, img, model_kwargs=model_kwargs)
         return device, img, indices
 
+    def _target_guide_args(self, cond_fn, x):
+        """A guidance.TargetGuide as the operands of MST_GUIDE_TARGET, checked against this process: the guide's alphas_cumprod is the
+        ORIGINAL process's table, so alphas_cumprod[timestep_map] must be this process's own -- the kernel reads sqrt(abar_t) from the
+        schedule's row, the Python form from the guide's table."""
+        follow = cond_fn.alphas_cumprod is not None
+        if follow:
+            if self.rescale_timesteps:
+                raise ValueError("TargetGuide: rescaled (float) timesteps cannot index alphas_cumprod")
+            tmap = np.asarray(getattr(self, "timestep_map", None) or self._identity_map())
+            ac = np.asarray(cond_fn.alphas_cumprod, dtype=np.float64)
+            if tmap.max() >= ac.shape[0] or not np.allclose(ac[tmap], self.alphas_cumprod, rtol=1e-9, atol=0.0):
+                raise ValueError("TargetGuide: alphas_cumprod[timestep_map] is not this diffusion's alphas_cumprod: pass the "
+                                 "ORIGINAL process's table (the one its timesteps index)")
+        return _eng.guide_args(x, target=cond_fn.target, mask=cond_fn.mask, weight=cond_fn.weight, follow_schedule=follow)
+
     def _engine_loop(self, sampler, denoiser, cfg, img, indices, clip_denoised, model_kwargs, const_noise, eta, progress,
-                     chunked, want_xstart=True):
+                     chunked, want_xstart=True, cond_fn=None):
         """Loop inside the library.  chunked=True (the non-progressive entry points): `noise_chunk`
         indices per native call, intermediate 'sample' entries are None; chunked=False (public
         progressive generators): one index per call and a fresh 'sample' tensor every step.
@@ -402,7 +480,12 @@ class GaussianDiffusion:
         # the philox source then draws ONE clip's numbers with the same generator (philox_normal, key seed + c0, step j) and hands them
         # to the loop as buffer noise repeated over the batch, in chunks bounded like the torch source's
         in_kernel = philox and not const_noise
-        if not chunked:
+        # cond_fn: a guidance.TargetGuide is computed inside the step kernel, so the loop stays one native call per noise chunk; any
+        # other callable is evaluated on x_t in front of every step (one step per engine call, no native loop, no graph)
+        from .guidance import TargetGuide
+        guide = self._target_guide_args(cond_fn, x) if isinstance(cond_fn, TargetGuide) else None
+        per_step = cond_fn is not None and guide is None
+        if not chunked or per_step:
             chunk = 1
         elif in_kernel:
             # no noise buffer; with an x0-hat dump the dump itself is bounded the same way
@@ -423,13 +506,16 @@ class GaussianDiffusion:
                 noise = th.stack([self._draw(x, const_noise) for _ in idx])
             elif not in_kernel:
                 noise = th.stack([eng.philox_normal(1, x.shape[-1], seed + c0, j).expand(x.shape) for j in range(len(idx))])
+            if per_step:
+                t = th.full((x.shape[0],), int(idx[0]), device=x.device, dtype=th.long)
+                guide = _eng.guide_args(x, grad=self._cond_gradient(cond_fn, x, t, model_kwargs))
             res = eng.sample_loop(sch, x, idx[0], idx[-1], sampler, eta, cfg=cfg is not None, scale=scale,
                                   mask=mask if mask is not None else nmask, motion=motion, mask_noise=nmask is not None,
-                                  clip_denoised=clip_denoised, noise=noise, seed=seed + c0, dump_xstart=want_xstart)
+                                  clip_denoised=clip_denoised, noise=noise, seed=seed + c0, dump_xstart=want_xstart, guide=guide)
             dump = res[1] if want_xstart else None
             for j in range(len(idx)):
                 end = j == len(idx) - 1
-                yield {"sample": (x if chunked else x.clone()) if end else None,
+                yield {"sample": (x if chunked and not per_step else x.clone()) if end else None,
                        "pred_xstart": dump[j] if want_xstart else None}
 
     def _sample_loop_progressive(self, ddim, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
@@ -466,10 +552,11 @@ class GaussianDiffusion:
         """The no-grad steps of every loop entry, from `img` as it is through `indices` in their order (descending for p_sample /
         ddim_sample, ascending for ddim_reverse_sample): inside the library when the denoiser is native, step by step otherwise."""
         denoiser, cfg, _ = _unwrap(model)
-        if (denoiser is not None and cond_fn is None and denoised_fn is None and not denoiser.training
-                and self.model_mean_type == ModelMeanType.START_X):
+        if (denoiser is not None and denoised_fn is None and not denoiser.training
+                and self.model_mean_type == ModelMeanType.START_X
+                and (cond_fn is None or sampler != _eng.SAMPLER_DDIM_REVERSE)):
             yield from self._engine_loop(sampler, denoiser, cfg, img, indices, clip_denoised, model_kwargs, const_noise, eta,
-                                         progress, chunked, want_xstart)
+                                         progress, chunked, want_xstart, cond_fn=cond_fn)
             return
         if progress:
             from tqdm.auto import tqdm
@@ -623,7 +710,8 @@ class GaussianDiffusion:
         if not int(order) or not 1 <= order <= 4:
             raise ValueError('order is invalid (should be int from 1-4).')
         if cond_fn is not None or denoised_fn is not None:
-            raise NotImplementedError("cond_fn / denoised_fn are never set by this code base (SURVEY.md section 9)")
+            raise NotImplementedError("plms_sample: cond_fn / denoised_fn are not built for the PLMS sampler (guided PLMS is out of scope); "
+                                      "p_sample, ddim_sample and their loops take them")
         sch = self._schedule(x.device)
         mask, motion = self._inpaint_pair(model_kwargs)
         mean_type = {ModelMeanType.START_X: 0, ModelMeanType.EPSILON: 1, ModelMeanType.PREVIOUS_X: 2}[self.model_mean_type]
@@ -687,7 +775,8 @@ class GaussianDiffusion:
         if not int(order) or not 1 <= order <= 4:
             raise ValueError('order is invalid (should be int from 1-4).')
         if cond_fn is not None or denoised_fn is not None:
-            raise NotImplementedError("cond_fn / denoised_fn are never set by this code base (SURVEY.md section 9)")
+            raise NotImplementedError("plms_sample: cond_fn / denoised_fn are not built for the PLMS sampler (guided PLMS is out of scope); "
+                                      "p_sample, ddim_sample and their loops take them")
         if order > 1 and indices[0] == 0:
             raise ValueError("plms_sample_loop: a chain of order > 1 cannot start at index 0 (its first step evaluates the model at t - 1)")
         denoiser, cfg, _ = _unwrap(model)
@@ -727,7 +816,8 @@ class GaussianDiffusion:
         if not int(order) or not 1 <= order <= 4:
             raise ValueError('order is invalid (should be int from 1-4).')
         if cond_fn is not None or denoised_fn is not None:
-            raise NotImplementedError("cond_fn / denoised_fn are never set by this code base (SURVEY.md section 9)")
+            raise NotImplementedError("plms_sample: cond_fn / denoised_fn are not built for the PLMS sampler (guided PLMS is out of scope); "
+                                      "p_sample, ddim_sample and their loops take them")
         if order > 1 and self.num_timesteps - skip_timesteps - 1 == 0:
             raise ValueError("plms_sample_loop: a chain of order > 1 cannot start at index 0 (its first step evaluates the model at t - 1)")
         device, img, indices = self._loop_setup(model, shape, noise, device, skip_timesteps, init_image, None, model_kwargs)

@@ -57,6 +57,10 @@ class SpacedDiffusion(GaussianDiffusion):
     def _model_output(self, model, x, t, model_kwargs):
         return super()._model_output(self._wrap_model(model), x, t, model_kwargs)
 
+    def _wrap_cond(self, cond_fn):
+        """The cond_fn sees timestep_map[t] (rescaled when the process rescales), as the model does (reference respace.py:104-108)."""
+        return self._wrap_model(cond_fn)
+
     def training_losses(self, model, *args, **kwargs):
         # the reference forwards to a base method that does not exist (respace.py:94-97); keep the
         # failure mode explicit instead of an AttributeError deep in super()

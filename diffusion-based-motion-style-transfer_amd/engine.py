@@ -15,6 +15,7 @@ SAMPLER_DDIM_REVERSE = 2        # x_t -> x_{t+1}, the deterministic DDIM step ru
 SAMPLER_PLMS = 3                # plms_sample (gaussian_diffusion.py:1084-1166): Pseudo Linear Multistep, orders 1..4; no noise term.
                                 # It carries a history, so it runs through sample_loop_plms / Schedule.plms_step, not sample_loop / step
 NOISE_BUFFER, NOISE_PHILOX = 0, 1
+GUIDE_GRADIENT, GUIDE_TARGET = 1, 2    # enum MST_GUIDE_*: a caller's gradient for one step / the target guide computed in the step kernel
 
 # Largest classifier-free guidance factor (the larger of s and 1 - s per clip) at which the default f16-operand path was measured to
 # stay within 1e-3 relative L2 of the fp32 reference with 10 % to spare: worst clip 8.3e-4 at 3.0, 1.10e-3 at 4.0 over both shapes and
@@ -55,7 +56,7 @@ class Schedule:
     """Device copy of one diffusion process (enum mst_table order), built from the float64 numpy
     tables of a GaussianDiffusion-like object or an `oracle.schedule`-style dict."""
 
-    def __init__(self, tables, timestep_map, device, log_variance=None):
+    def __init__(self, tables, timestep_map, device, log_variance=None, variance=None):
         get = (lambda k: tables[k]) if isinstance(tables, dict) else (lambda k: getattr(tables, k))
         if log_variance is None:
             log_variance = get("posterior_log_variance_clipped")      # FIXED_SMALL
@@ -72,6 +73,15 @@ class Schedule:
         N.check(N.lib().mst_schedule_create(self.num_steps, tab.ctypes.data_as(C.c_void_p),
                                             tmap.ctypes.data_as(C.c_void_p), self.device.index or 0, C.byref(h)))
         self.handle = h
+        # the variance row (p_mean_var["variance"], read by the guided ancestral step alone): FIXED_SMALL unless the caller says otherwise
+        if variance is None:
+            try:
+                variance = get("posterior_variance")
+            except (KeyError, AttributeError):      # a hand-made table set without it: guided ancestral steps are then refused by name
+                return
+        var = np.ascontiguousarray(np.asarray(variance, dtype=np.float64).astype(np.float32))
+        assert var.shape == (self.num_steps,)
+        N.check(N.lib().mst_schedule_set_variance(h, var.ctypes.data_as(C.c_void_p)))
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -109,6 +119,28 @@ class Schedule:
         N.check(N.lib().mst_step_epilogue_mt(self.handle, N.ptr(mo), N.ptr(x), N.ptr(noise), N.ptr(mask), N.ptr(motion),
                                              N.ptr(t), B, x.numel() // B, int(sampler), int(mean_type), float(eta), int(bool(mask_noise)),
                                              int(bool(clip_denoised)), N.ptr(sample), N.ptr(xstart), N.stream_ptr(dev)))
+        return sample, xstart
+
+    def step_guided(self, model_output, x, t, noise, guide, sampler=SAMPLER_DDPM, eta=0.0, mask=None, motion=None,
+                    mask_noise=False, clip_denoised=False, mean_type=0):
+        """(sample, pred_xstart) of one p_sample / ddim_sample step with a cond_fn, given the model output (reference :577-580 with
+        condition_mean :454-467; :821-846 with condition_score :484-506).  guide: a `guide_args(...)` pair.  pred_xstart is the
+        UNGUIDED x0-hat, as the reference returns it."""
+        dev = x.device
+        mo = _f32c(model_output, dev, "model_output")
+        x = _f32c(x, dev, "x")
+        noise = None if noise is None else _f32c(noise, dev, "noise")
+        mask = None if mask is None else _f32c(mask, dev, "mask")
+        motion = None if motion is None else _f32c(motion, dev, "motion")
+        t = t.to(device=dev, dtype=torch.int64).contiguous()
+        g, keep = guide
+        sample, xstart = torch.empty_like(x), torch.empty_like(x)
+        B = x.shape[0]
+        N.check(N.lib().mst_step_epilogue_guided(self.handle, N.ptr(mo), N.ptr(x), N.ptr(noise), N.ptr(mask), N.ptr(motion),
+                                                 N.ptr(t), B, x.numel() // B, int(sampler), int(mean_type), float(eta),
+                                                 int(bool(mask_noise)), int(bool(clip_denoised)), C.byref(g), N.ptr(sample),
+                                                 N.ptr(xstart), N.stream_ptr(dev)))
+        del keep
         return sample, xstart
 
     def plms_step(self, model_output, x, t, history=(), order=None, mask=None, motion=None, clip_denoised=False, mean_type=0,
@@ -152,6 +184,37 @@ class Schedule:
         N.check(N.lib().mst_plms_euler(self.handle, N.ptr(mo), N.ptr(x_mid), N.ptr(x), N.ptr(eps), N.ptr(mask), N.ptr(motion), N.ptr(t), B,
                                        x.numel() // B, int(mean_type), int(bool(clip_denoised)), N.ptr(sample), N.stream_ptr(dev)))
         return sample
+
+
+def guide_args(x, grad=None, target=None, mask=None, weight=None, follow_schedule=False):
+    """(MstGuideArgs, tensors it points to) for a step or loop on `x` ([B,F,1,T]): grad -> MST_GUIDE_GRADIENT (the gradient of one
+    step), otherwise MST_GUIDE_TARGET with g = weight[b] mask (a_t target - x_t); target / mask broadcast to x's shape, weight to [B]."""
+    dev = x.device
+    g = N.MstGuideArgs()
+    keep = []
+
+    def full(v, what):
+        v = _f32c(v, dev, what)
+        if v.shape != x.shape:
+            v = v.expand(x.shape).contiguous()
+        keep.append(v)
+        return v.data_ptr()
+    if grad is not None:
+        g.kind, g.grad_dev = GUIDE_GRADIENT, full(grad, "grad")
+        return g, keep
+    g.kind, g.follow_schedule = GUIDE_TARGET, int(bool(follow_schedule))
+    if target is not None:
+        g.target_dev = full(target, "target")
+    if mask is not None:
+        g.mask_dev = full(mask, "guide mask")
+    if weight is not None:
+        w = _f32c(torch.as_tensor(weight, dtype=torch.float32).reshape(-1), dev, "weight")
+        if w.numel() == 1:
+            w = w.expand(x.shape[0]).contiguous()
+        assert w.numel() == x.shape[0], "weight: a scalar or one value per clip"
+        keep.append(w)
+        g.weight_dev = w.data_ptr()
+    return g, keep
 
 
 def plan_style_segments(styles, S, tile_rows):
@@ -456,10 +519,12 @@ class DenoiserEngine:
     # ------------------------------------------------------------------------------ sampling
     def sample_loop(self, schedule, x, t_start, t_end=0, sampler=SAMPLER_DDPM, eta=0.0, cfg=False, scale=None,
                     mask=None, motion=None, mask_noise=True, clip_denoised=False, noise=None, seed=None,
-                    dump_xstart=False):
+                    dump_xstart=False, guide=None):
         """Run diffusion indices t_start..t_end in place on `x` ([B,F,1,T] float32 GPU tensor): downward (t_start >= t_end) for
         SAMPLER_DDPM / SAMPLER_DDIM, upward (t_start <= t_end; x leaves as x at index t_end + 1) for SAMPLER_DDIM_REVERSE.
         noise: [nsteps,B,F,1,T] tensor (injected draws) or None -> in-kernel Philox with `seed`; the reverse sampler reads neither.
+        guide: a `guide_args(...)` pair -> mst_sample_loop_guided (p_sample_loop / ddim_sample_loop with a cond_fn); the x0-hat dump is
+        then the UNGUIDED x0-hat of every step.
         Returns x (and the [nsteps,B,F,1,T] x0-hat dump, entry j = executed step j, when requested)."""
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         if cfg:
@@ -488,7 +553,11 @@ class DenoiserEngine:
         if dump_xstart:
             dump = torch.empty((nsteps,) + tuple(x.shape), dtype=torch.float32, device=self.device)
             a.xstart_dump_dev = dump.data_ptr()
-        N.check(N.lib().mst_sample_loop(self.handle, schedule.handle, C.byref(a), N.stream_ptr(self.device)))
+        if guide is not None:
+            N.check(N.lib().mst_sample_loop_guided(self.handle, schedule.handle, C.byref(a), C.byref(guide[0]), N.stream_ptr(self.device)))
+            keep.append(guide[1])
+        else:
+            N.check(N.lib().mst_sample_loop(self.handle, schedule.handle, C.byref(a), N.stream_ptr(self.device)))
         self._loop_keepalive = keep
         return (x, dump) if dump_xstart else x
 

@@ -104,6 +104,12 @@ enum mst_table {
 int  mst_schedule_create(int32_t num_steps, const float* tables_host,
                          const int32_t* timestep_map_host, int32_t device, mst_schedule** out);
 void mst_schedule_destroy(mst_schedule* s);
+/* The variance row of the schedule, float32 [num_steps] on the host: p_mean_var["variance"] of p_mean_variance
+ * (gaussian_diffusion.py:366-385) -- posterior_variance for FIXED_SMALL (exactly 0 at index 0), append(posterior_variance[1],
+ * betas[1:]) for FIXED_LARGE.  It is NOT exp(MST_TAB_LOGVAR).  Only condition_mean reads it (:463-467: mean += variance * gradient),
+ * so only a guided MST_SAMPLER_DDPM step needs it, and such a step on a schedule without the row is refused by name.  An entry of
+ * its own: mst_schedule_create's signature and the MST_TAB_* layout are unchanged. */
+int  mst_schedule_set_variance(mst_schedule* s, const float* variance_host);
 
 /* -------------------------------------------------------------------------------------------
  * conditioning: replaces embed_text(mask_cond(encode_text(...))) of StyleDiffusion.forward
@@ -198,6 +204,37 @@ typedef struct mst_plms_args {
 int mst_sample_loop_plms(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_plms_args* pl, void* stream);
 
 
+/* -----------------------------------------------------------------------------------------
+ * Guided sampling: the `cond_fn` argument of p_sample / ddim_sample and their loops (condition_mean, gaussian_diffusion.py:454-467,
+ * called at :577-580 and inpainting_gaussian_diffusion.py:59-62; condition_score, :484-506, called at :821-824 and igd:150-153).
+ * g = grad log p(y | x_t), float32 [B,F,1,T] (B rows under CFG too, not 2B), enters the fused step behind the model output:
+ *   MST_SAMPLER_DDPM   mean += variance_t g (the row of mst_schedule_set_variance), then the noise term;
+ *   MST_SAMPLER_DDIM   eps = (srac x - pred) / srm1ac; eps -= sqrtf(1 - abar_t) g; pred' = srac x - srm1ac eps; eps re-derived from
+ *                      pred'; sample = pred' sqrt(abar_prev) + dir eps'' + sigma noise.
+ * The x0-hat dump holds the UNGUIDED x0-hat (the reference returns out_orig["pred_xstart"], :847 / igd:177).  Blend, conversion,
+ * clip, noise and noise mask are those of mst_sample_loop; so are slices, CFG, style slots, precise mode, graph replay and profiling.
+ *   MST_GUIDE_GRADIENT  grad_dev is g for ONE step (a Python cond_fn does not depend on the model output: the caller evaluates
+ *                       it on x_t first).  t_start must equal t_end.
+ *   MST_GUIDE_TARGET    g = weight[b] mask (a_t target - x_t), computed inside the step kernel from operands that are constant over
+ *                       the loop: target_dev [B,F,1,T], mask_dev [B,F,1,T] or NULL (all ones), weight_dev [B]; a_t = 1, or
+ *                       MST_TAB_SQRT_AC at the step's index when follow_schedule != 0 (a Gaussian log-likelihood around
+ *                       sqrt(abar_t) target: a soft keyframe / trajectory constraint).  A k-step call equals k one-step calls bit
+ *                       for bit, and one captured graph serves every step.
+ * Refused, each by name: MST_GUIDE_GRADIENT with t_start != t_end; any guide with MST_SAMPLER_DDIM_REVERSE (ddim_reverse_sample
+ * has no cond_fn, :910-919) or MST_SAMPLER_PLMS (guided PLMS is not built); a guided MST_SAMPLER_DDPM step on a schedule without the
+ * variance row; a NULL grad_dev (gradient kind), target_dev or weight_dev (target kind).
+ * ----------------------------------------------------------------------------------------- */
+enum { MST_GUIDE_GRADIENT = 1, MST_GUIDE_TARGET = 2 };
+typedef struct mst_guide_args {
+    int32_t kind;                   /* MST_GUIDE_GRADIENT or MST_GUIDE_TARGET                          */
+    int32_t follow_schedule;        /* target kind: a_t = sqrt(abar_t) instead of 1                    */
+    const float* grad_dev;          /* gradient kind: [B,F,1,T] float32                                */
+    const float* target_dev;        /* target kind: [B,F,1,T] float32                                  */
+    const float* mask_dev;          /* target kind: [B,F,1,T] float32, or NULL for all ones            */
+    const float* weight_dev;        /* target kind: [B] float32                                        */
+} mst_guide_args;
+int mst_sample_loop_guided(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_guide_args* g, void* stream);
+
 /* Number of independent clip slices (1..3) mst_sample_loop runs on separate streams for this
  * batch of `frames`-frame clips (frames <= 0: the engine's max_frames; the policy depends on the
  * token-row count, so pass the loop's own frame count when it is below the cap): clips never interact (no cross-sample op in
@@ -238,6 +275,16 @@ int mst_step_epilogue_mt(const mst_schedule* s, const float* model_out_dev, cons
                          const int64_t* t_dev, int32_t batch, int64_t per_clip, int32_t sampler, int32_t mean_type,
                          float eta, int32_t mask_noise, int32_t clip_denoised,
                          float* sample_out_dev, float* xstart_out_dev, void* stream);
+
+/* mst_step_epilogue_mt with a guide (p_sample / ddim_sample with a cond_fn for callers that bring their own model: gaussian_diffusion.py
+ * :577-580 with condition_mean :454-467, :821-824 with condition_score :484-506, then :828-846).  g as in mst_sample_loop_guided, with
+ * per-clip indices t_dev; weight_dev is [batch].  xstart_out_dev receives the UNGUIDED x0-hat.  sampler: MST_SAMPLER_DDPM or
+ * MST_SAMPLER_DDIM (the others are refused by name, as is MST_SAMPLER_DDPM on a schedule without the variance row). */
+int mst_step_epilogue_guided(const mst_schedule* s, const float* model_out_dev, const float* x_dev,
+                             const float* noise_dev, const float* mask_dev, const float* motion_dev,
+                             const int64_t* t_dev, int32_t batch, int64_t per_clip, int32_t sampler, int32_t mean_type,
+                             float eta, int32_t mask_noise, int32_t clip_denoised, const mst_guide_args* g,
+                             float* sample_out_dev, float* xstart_out_dev, void* stream);
 
 /* plms_sample for callers that bring their own model (gaussian_diffusion.py:1084-1166), elementwise on [batch][per_clip] tensors.
  *   mst_plms_epilogue   the multistep step: cur_order 1..4, e1 / e2 / e3 the history NEWEST FIRST (only cur_order - 1 are read, the
