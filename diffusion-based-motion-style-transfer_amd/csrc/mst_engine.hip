@@ -3102,11 +3102,28 @@ extern "C" int mst_adamw_step(int32_t n_tensors, float* const* params, const flo
 }
 
 // ------------------------------------------------------------------------------------------ post-sampling ABI
+// k_recover_from_ric keeps ang / px / pz / cs / sn, five fp32 rows of `frames` entries, in dynamic LDS: what one workgroup may ask for
+// on the current device bounds the clip length, 4096 frames at the most.
+extern "C" int mst_recover_max_frames(void) {
+    int dev = 0, lds = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        fail("mst_recover_max_frames: the device's shared memory per block cannot be read");
+        return -1;
+    }
+    const int n = lds / (int)(5 * sizeof(float));
+    return n < 4096 ? n : 4096;
+}
 extern "C" int mst_recover_from_ric(const float* sample, const float* mean, const float* stdv, int32_t batch, int32_t feats,
                                     int32_t frames, int32_t joints, float* out, void* stream) {
     if (!sample || !mean || !stdv || !out || batch < 1 || frames < 1 || joints < 1) return fail("mst_recover_from_ric: bad arguments");
     if (feats < 4 + 3 * (joints - 1)) return fail("mst_recover_from_ric: %d features cannot hold %d joints", feats, joints);
-    if (frames > 4096) return fail("mst_recover_from_ric: frames %d > 4096", frames);
+    const int max_frames = mst_recover_max_frames();
+    if (max_frames < 0) return 1;
+    if (frames > max_frames)
+        return fail("mst_recover_from_ric: frames %d > %d (five fp32 rows of `frames` entries in LDS, capped at 4096)", frames, max_frames);
+    // (above 64 KB a launch needs the per-device opt-in; asked once, for the longest clip the device takes)
+    if (sizeof(float) * 5 * frames > 64 * 1024) CHECK(ensure_dyn_lds((const void*)k_recover_from_ric, (int)sizeof(float) * 5 * max_frames));
     hipLaunchKernelGGL(k_recover_from_ric, dim3(batch), dim3(256), sizeof(float) * 5 * frames, (hipStream_t)stream, sample, mean, stdv,
                        feats, frames, joints, out);
     HIPCHECK(hipGetLastError());

@@ -13,6 +13,7 @@ import ctypes as C
 import torch
 
 from .. import _native as N
+from .. import engine as _eng
 
 
 def _cuda_f32(t, what):
@@ -24,6 +25,9 @@ def _cuda_f32(t, what):
 class FusedStepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model_out, x, t, noise, mask, motion, schedule, sampler, eta, mask_noise, clip_denoised):
+        # the operands as the kernels read them (engine._operand: full size, float32, contiguous), fixed HERE so that backward hands
+        # k_step_backward the very mask buffer the forward kernel used, not the caller's (possibly broadcastable, bool or float64) one
+        mask, motion = _eng._mask_pair(mask, motion, x.shape, x.device)
         sample, pred = schedule.step(model_out.detach(), x, t, noise, sampler, eta, mask=mask, motion=motion,
                                      mask_noise=mask_noise, clip_denoised=clip_denoised)
         ctx.schedule, ctx.sampler, ctx.eta = schedule, int(sampler), float(eta)
@@ -46,7 +50,7 @@ class FusedStepFn(torch.autograd.Function):
         d = torch.empty_like(ref, memory_format=torch.contiguous_format)
         B = d.shape[0]
         tt = t.to(device=d.device, dtype=torch.int64).contiguous()
-        mk = None if mask is None else mask.to(device=d.device, dtype=torch.float32).contiguous()
+        mk = None if mask is None else _eng._operand(mask, d.shape, "inpainting_mask", _eng.RULE_EQUAL, d.device)      # (as saved: no copy)
         N.check(N.lib().mst_step_backward(ctx.schedule.handle, N.ptr(gs), N.ptr(gp), N.ptr(mk), int(ctx.has_blend), N.ptr(tt), B,
                                           d.numel() // B, ctx.sampler, ctx.eta, N.ptr(pred_clipped), N.ptr(d), N.stream_ptr(d.device)))
         return (d,) + (None,) * 10

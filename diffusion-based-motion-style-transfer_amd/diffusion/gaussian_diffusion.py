@@ -327,6 +327,8 @@ class GaussianDiffusion:
         reverse = sampler == _eng.SAMPLER_DDIM_REVERSE
         noise = None if reverse else self._draw(x, const_noise)
         mask, motion = self._inpaint_pair(model_kwargs)
+        if mask is not None:
+            assert out.shape == mask.shape == motion.shape      # (reference :344; the noise mask alone may broadcast, engine._mask_pair)
         nmask = None if reverse else self._noise_mask(model_kwargs)      # (no noise, no noise mask: y needs no 'inpainting_mask', :910-946)
         # epsilon / previous-x models: converted to x0-hat INSIDE the step kernel (MODEs of k_step_epilogue), behind the inpainting blend
         # as the reference orders them (:341-349 then :398-412)
@@ -404,9 +406,7 @@ class GaussianDiffusion:
         sch = self._schedule(x.device)
         with th.enable_grad():
             sample, pred = FusedStepFn.apply(out, x.contiguous().float(), t, noise.contiguous().float(),
-                                             None if (mask if mask is not None else nmask) is None else
-                                             (mask if mask is not None else nmask).contiguous().float(),
-                                             None if motion is None else motion.contiguous().float(), sch,
+                                             mask if mask is not None else nmask, motion, sch,      # (brought to x's shape in the node)
                                              _eng.SAMPLER_DDIM if ddim else _eng.SAMPLER_DDPM, eta, nmask is not None, clip_denoised)
         return {"sample": sample, "pred_xstart": pred if pred_xstart_in_graph else pred.detach()}
 
@@ -471,6 +471,8 @@ class GaussianDiffusion:
         denoiser.mst_prepare(eng, y, cfg is not None)
         reverse = sampler == _eng.SAMPLER_DDIM_REVERSE      # no noise term: no buffer, no seed, no noise mask, no draw from torch's generator
         mask, motion = self._inpaint_pair(model_kwargs)
+        if mask is not None:
+            assert img.shape == mask.shape == motion.shape      # (reference :344, what every step of the loop would assert)
         nmask = None if reverse else self._noise_mask(model_kwargs)
         scale = y['scale'] if cfg is not None else None
         sch = self._schedule(img.device)
@@ -718,6 +720,8 @@ class GaussianDiffusion:
         kw = dict(mask=mask, motion=motion, clip_denoised=clip_denoised, mean_type=mean_type)
         with th.no_grad():
             out = self._model_output(model, x, t, model_kwargs)
+            if mask is not None:
+                assert out.shape == mask.shape == motion.shape      # (reference :344)
             if order > 1 and old_out is None:
                 if bool((t == 0).any()):
                     raise ValueError("plms_sample: a chain of order > 1 cannot start at index 0 (its first step evaluates the model at t - 1)")
@@ -741,6 +745,8 @@ class GaussianDiffusion:
         eng = denoiser.mst_engine(img.shape[0] * (2 if cfg is not None else 1), img.shape[-1])
         denoiser.mst_prepare(eng, y, cfg is not None)
         mask, motion = self._inpaint_pair(model_kwargs)
+        if mask is not None:
+            assert img.shape == mask.shape == motion.shape      # (reference :344)
         scale = y['scale'] if cfg is not None else None
         sch = self._schedule(img.device)
         x = img.contiguous().float().clone()

@@ -41,15 +41,75 @@ LAYER_TENSORS = (
     "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")
 
 
+def _need_gpu(t, what):
+    if t.device.type != "cuda":
+        raise RuntimeError(f"{what}: the engine needs a GPU tensor")
+    return t
+
+
 def _f32c(t, device, what):
     if not isinstance(t, torch.Tensor):
         t = torch.as_tensor(np.asarray(t))
     t = t.to(device=device, dtype=torch.float32)
     if not t.is_contiguous():
         t = t.contiguous()
-    if t.device.type != "cuda":
-        raise RuntimeError(f"{what}: the engine needs a GPU tensor")
-    return t
+    return _need_gpu(t, what)
+
+
+# The operand contract ("Drop-in boundary"): the kernels read every operand as base + i over the target's element
+# count and cannot see a shape, so each operand is brought to exactly the target's shape here, by the rule the reference applies to it.
+RULE_EQUAL = "equal"            # `assert model_output.shape == inpainting_mask.shape == inpainted_motion.shape` (gaussian_diffusion.py:344)
+RULE_BROADCAST = "broadcast"    # `noise *= 1. - y['inpainting_mask']` (inpainting_gaussian_diffusion.py:18): whatever broadcasts to the noise
+RULE_SCALE = "scale"            # `y['scale'].view(-1, 1, 1, 1)` (cfg_sampler.py): one value, or one per clip
+
+
+def _fit(t, target_shape, what, rule):
+    """The shape half of `_operand`, on whatever device `t` lives: a float32 contiguous tensor of exactly `target_shape`, or the error
+    the reference (or torch, on its behalf) raises for such an operand.  bool / float64 go to float32 as `ones * mask` does (:346-348)."""
+    target = tuple(int(v) for v in target_shape)
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(np.asarray(t))
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    if rule == RULE_EQUAL:
+        assert tuple(t.shape) == target, f"{what}: shape {tuple(t.shape)} is not {target}"
+    elif rule == RULE_BROADCAST:
+        if tuple(t.shape) != target:
+            try:
+                t = t.expand(target)
+            except RuntimeError as e:
+                raise RuntimeError(f"{what}: shape {tuple(t.shape)} does not broadcast to {target} ({e})") from None
+    elif rule == RULE_SCALE:
+        assert len(target) == 1
+        t = t.reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(target)
+        elif t.numel() != target[0]:
+            raise ValueError(f"{what}: {t.numel()} values for {target[0]} clips (one value, or one per clip)")
+    else:
+        raise ValueError(f"{what}: unknown operand rule {rule!r}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _operand(t, target_shape, what, rule, device=None):
+    """`t` as the kernels need it: float32, contiguous, on the GPU (`device`, or where it is) and of exactly `target_shape`."""
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(np.asarray(t))
+    if device is not None:
+        t = t.to(device=device)
+    return _need_gpu(_fit(t, target_shape, what, rule), what)
+
+
+def _mask_pair(mask, motion, shape, device):
+    """(mask, motion) of a step on a tensor of `shape`: with a motion the two are the reference's inpainting pair (equal shapes); a mask
+    alone is only ever the noise mask, which broadcasts."""
+    if motion is not None:
+        motion = _operand(motion, shape, "inpainted_motion", RULE_EQUAL, device)
+        if mask is not None:
+            mask = _operand(mask, shape, "inpainting_mask", RULE_EQUAL, device)
+    elif mask is not None:
+        mask = _operand(mask, shape, "inpainting_mask (noise mask)", RULE_BROADCAST, device)
+    return mask, motion
 
 
 class Schedule:
@@ -93,8 +153,8 @@ class Schedule:
     def q_sample(self, x_start, t, noise, mask=None):
         dev = x_start.device
         x_start = _f32c(x_start, dev, "x_start")
-        noise = _f32c(noise, dev, "noise")
-        mask = None if mask is None else _f32c(mask, dev, "mask")
+        noise = _operand(noise, x_start.shape, "noise", RULE_EQUAL, dev)
+        mask, _ = _mask_pair(mask, None, x_start.shape, dev)
         t = t.to(device=dev, dtype=torch.int64).contiguous()
         out = torch.empty_like(x_start)
         B = x_start.shape[0]
@@ -108,11 +168,10 @@ class Schedule:
         mean_type: what the model predicts -- 0 x_start, 1 epsilon, 2 previous x (converted inside the kernel, reference :398-412).
         SAMPLER_DDIM_REVERSE draws nothing: `noise` may be None and is never read, `eta` must be 0."""
         dev = x.device
-        mo = _f32c(model_output, dev, "model_output")
         x = _f32c(x, dev, "x")
-        noise = None if noise is None else _f32c(noise, dev, "noise")
-        mask = None if mask is None else _f32c(mask, dev, "mask")
-        motion = None if motion is None else _f32c(motion, dev, "motion")
+        mo = _operand(model_output, x.shape, "model_output", RULE_EQUAL, dev)
+        noise = None if noise is None else _operand(noise, x.shape, "noise", RULE_EQUAL, dev)
+        mask, motion = _mask_pair(mask, motion, x.shape, dev)
         t = t.to(device=dev, dtype=torch.int64).contiguous()
         sample, xstart = torch.empty_like(x), torch.empty_like(x)
         B = x.shape[0]
@@ -127,11 +186,10 @@ class Schedule:
         condition_mean :454-467; :821-846 with condition_score :484-506).  guide: a `guide_args(...)` pair.  pred_xstart is the
         UNGUIDED x0-hat, as the reference returns it."""
         dev = x.device
-        mo = _f32c(model_output, dev, "model_output")
         x = _f32c(x, dev, "x")
-        noise = None if noise is None else _f32c(noise, dev, "noise")
-        mask = None if mask is None else _f32c(mask, dev, "mask")
-        motion = None if motion is None else _f32c(motion, dev, "motion")
+        mo = _operand(model_output, x.shape, "model_output", RULE_EQUAL, dev)
+        noise = None if noise is None else _operand(noise, x.shape, "noise", RULE_EQUAL, dev)
+        mask, motion = _mask_pair(mask, motion, x.shape, dev)
         t = t.to(device=dev, dtype=torch.int64).contiguous()
         g, keep = guide
         sample, xstart = torch.empty_like(x), torch.empty_like(x)
@@ -151,12 +209,11 @@ class Schedule:
         be the oldest history entry: a ring).  first_half=True: the first half of the Euler step that opens a chain of order > 1 --
         'sample' is then x_mid = pred sqrt(abar_prev) + sqrt(1 - abar_prev) eps and the history is not read."""
         dev = x.device
-        mo = _f32c(model_output, dev, "model_output")
         x = _f32c(x, dev, "x")
-        mask = None if mask is None else _f32c(mask, dev, "mask")
-        motion = None if motion is None else _f32c(motion, dev, "motion")
+        mo = _operand(model_output, x.shape, "model_output", RULE_EQUAL, dev)
+        mask, motion = _mask_pair(mask, motion, x.shape, dev)
         t = t.to(device=dev, dtype=torch.int64).contiguous()
-        hist = [_f32c(h, dev, "history") for h in history]
+        hist = [_operand(h, x.shape, "history", RULE_EQUAL, dev) for h in history]
         cur = 1 + len(hist) if order is None else min(int(order), 1 + len(hist))
         if not first_half and not 1 <= cur <= 4:
             raise ValueError("order is invalid (should be int from 1-4).")
@@ -175,9 +232,9 @@ class Schedule:
         """The second half of the Euler step (reference :1138-1141): `model_output` is the model at (x_mid, t - 1), `x` the chain's
         original input, `eps` the first evaluation's; `t` the step's own indices (>= 1).  Returns the sample."""
         dev = x.device
-        mo, x_mid, x, eps = (_f32c(v, dev, n) for v, n in ((model_output, "model_output"), (x_mid, "x_mid"), (x, "x"), (eps, "eps")))
-        mask = None if mask is None else _f32c(mask, dev, "mask")
-        motion = None if motion is None else _f32c(motion, dev, "motion")
+        x = _f32c(x, dev, "x")
+        mo, x_mid, eps = (_operand(v, x.shape, n, RULE_EQUAL, dev) for v, n in ((model_output, "model_output"), (x_mid, "x_mid"), (eps, "eps")))
+        mask, motion = _mask_pair(mask, motion, x.shape, dev)
         t = t.to(device=dev, dtype=torch.int64).contiguous()
         sample = torch.empty_like(x)
         B = x.shape[0]
@@ -194,9 +251,7 @@ def guide_args(x, grad=None, target=None, mask=None, weight=None, follow_schedul
     keep = []
 
     def full(v, what):
-        v = _f32c(v, dev, what)
-        if v.shape != x.shape:
-            v = v.expand(x.shape).contiguous()
+        v = _operand(v, x.shape, what, RULE_BROADCAST, dev)
         keep.append(v)
         return v.data_ptr()
     if grad is not None:
@@ -390,6 +445,8 @@ class DenoiserEngine:
             self.text_rows = te.shape[0]
             return
         kp = None if keep is None else _f32c(keep, self.device, "keep")
+        if kp is not None and kp.numel() != te.shape[0]:
+            raise ValueError(f"set_text: a keep mask of {kp.numel()} entries for {te.shape[0]} text embeddings")
         N.check(N.lib().mst_set_text(self.handle, N.ptr(te), N.ptr(kp), te.shape[0], int(bool(cfg)),
                                      N.stream_ptr(self.device)))
         self._text_keepalive = (te, kp)
@@ -401,7 +458,7 @@ class DenoiserEngine:
         B, F, one, T = x.shape
         assert F * one == self.feats, (F, one, self.feats)
         t = t.to(device=self.device, dtype=torch.int64).contiguous()
-        sc = None if scale is None else _f32c(scale, self.device, "scale")
+        sc = None if scale is None else _operand(scale, (B,), "scale", RULE_SCALE, self.device)
         out = torch.empty_like(x)
         N.check(N.lib().mst_forward(self.handle, N.ptr(x), N.ptr(t), N.ptr(sc), B, T, int(bool(cfg)), N.ptr(out),
                                     N.stream_ptr(self.device)))
@@ -526,7 +583,7 @@ class DenoiserEngine:
         guide: a `guide_args(...)` pair -> mst_sample_loop_guided (p_sample_loop / ddim_sample_loop with a cond_fn); the x0-hat dump is
         then the UNGUIDED x0-hat of every step.
         Returns x (and the [nsteps,B,F,1,T] x0-hat dump, entry j = executed step j, when requested)."""
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        assert _need_gpu(x, "x").dtype == torch.float32 and x.is_contiguous()
         if cfg:
             self.check_guidance_scale(scale)
         B, F, one, T = x.shape
@@ -537,15 +594,18 @@ class DenoiserEngine:
         a.t_start, a.t_end, a.eta = int(t_start), int(t_end), float(eta)
         keep = []
         if noise is not None:
-            noise = _f32c(noise, self.device, "noise")
             assert noise.numel() == nsteps * x.numel(), (noise.shape, nsteps, x.shape)
+            # every step's draw has x's shape: [nsteps, B, F, 1, T], or x's own shape for a single step
+            single = nsteps == 1 and isinstance(noise, torch.Tensor) and noise.dim() == x.dim()
+            noise = _operand(noise, tuple(x.shape) if single else (nsteps,) + tuple(x.shape), "noise", RULE_EQUAL, self.device)
             a.noise_mode, a.noise_dev = NOISE_BUFFER, noise.data_ptr()
             keep.append(noise)
         else:
             a.noise_mode, a.seed = NOISE_PHILOX, int(seed or 0)
+        mask, motion = _mask_pair(mask, motion, x.shape, self.device)
+        scale = None if scale is None else _operand(scale, (B,), "scale", RULE_SCALE, self.device)
         for name, val in (("scale_dev", scale), ("inpainting_mask_dev", mask), ("inpainted_motion_dev", motion)):
             if val is not None:
-                val = _f32c(val, self.device, name)
                 keep.append(val)
                 setattr(a, name, val.data_ptr())
         a.x_dev = x.data_ptr()
@@ -568,7 +628,7 @@ class DenoiserEngine:
         chain: for order > 1 its first step is the two-evaluation Euler step).  A k-step call equals k one-step calls with steps_done
         carried forward, bit for bit.  Returns x (and the x0-hat dump, first evaluation of every step, when requested).
         noise, seed, eta, mask_noise: handed to the library as given and ignored there (the step has no noise term)."""
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        assert _need_gpu(x, "x").dtype == torch.float32 and x.is_contiguous()
         if cfg:
             self.check_guidance_scale(scale)
         B, F, one, T = x.shape
@@ -588,9 +648,10 @@ class DenoiserEngine:
                 "hist: a contiguous float32 [3,B,F,1,T] ring"
             pl.hist_dev = hist.data_ptr()
             keep.append(hist)
+        mask, motion = _mask_pair(mask, motion, x.shape, self.device)
+        scale = None if scale is None else _operand(scale, (B,), "scale", RULE_SCALE, self.device)
         for name, val in (("scale_dev", scale), ("inpainting_mask_dev", mask), ("inpainted_motion_dev", motion)):
             if val is not None:
-                val = _f32c(val, self.device, name)
                 keep.append(val)
                 setattr(a, name, val.data_ptr())
         a.x_dev = x.data_ptr()

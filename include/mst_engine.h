@@ -255,6 +255,12 @@ int mst_loop_slices(const mst_engine* e, int32_t batch, int32_t cfg, int32_t fra
  *                       gaussian_diffusion.py:910-946 (ddim_reverse_sample: sampler MST_SAMPLER_DDIM_REVERSE, eta 0,
  *                       noise_dev never read and may be NULL)
  * t_dev is int64 [batch] of indices into the schedule.  sample_out_dev / xstart_out_dev may be NULL.
+ *
+ * THE CALLER IS TRUSTED.  Every tensor operand of this section (and of mst_step_backward, mst_plms_epilogue / mst_plms_euler below)
+ * is read as base + i over batch * per_clip float32 elements, the scale / weight vectors over `batch`: nothing here can see a
+ * tensor's shape, and no check that would cost a synchronisation is made.  A broadcastable mask, a one-element scale or a
+ * one-clip motion must be expanded to full size BEFORE the call; the Python handles do that (engine.py `_operand`, the table in
+ * DESIGN.md section 1, "Drop-in boundary"), other callers owe the same.
  * ----------------------------------------------------------------------------------------- */
 int mst_q_sample(const mst_schedule* s, const float* x_start_dev, const float* noise_dev,
                  const float* mask_dev, const int64_t* t_dev, int32_t batch, int64_t per_clip,
@@ -441,6 +447,9 @@ int mst_adamw_step(int32_t n_tensors, float* const* params, const float* const* 
  * ----------------------------------------------------------------------------------------- */
 int mst_recover_from_ric(const float* sample_dev, const float* mean_dev, const float* std_dev, int32_t batch,
                          int32_t feats, int32_t frames, int32_t joints, float* out_dev, void* stream);
+/* Longest clip mst_recover_from_ric takes on the current device: the kernel keeps five fp32 rows of `frames` entries in dynamic LDS,
+ * so this is min(4096, shared memory per block / 20 bytes); longer clips are refused on the host.  -1 when the device cannot be asked. */
+int mst_recover_max_frames(void);
 
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
