@@ -29,6 +29,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_embed.h"
 #include "mst_small.h"
 #include "mst_style.h"
+#include "mst_feet.h"
 
 using namespace mst;
 
@@ -3126,6 +3127,76 @@ extern "C" int mst_recover_from_ric(const float* sample, const float* mean, cons
     if (sizeof(float) * 5 * frames > 64 * 1024) CHECK(ensure_dyn_lds((const void*)k_recover_from_ric, (int)sizeof(float) * 5 * max_frames));
     hipLaunchKernelGGL(k_recover_from_ric, dim3(batch), dim3(256), sizeof(float) * 5 * frames, (hipStream_t)stream, sample, mean, stdv,
                        feats, frames, joints, out);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// Foot-skate cleanup (mst_feet.h).  The clip length is bounded by the two contact maps k_remove_fs keeps in LDS (8 bytes a frame) and
+// capped where mst_recover_from_ric is, so that whatever that returns can be cleaned; the filter's forward result lives in the
+// caller's workspace, not in LDS, so the bound does not fall with the joint count.
+extern "C" int mst_remove_fs_max_frames(int32_t joints) {
+    if (joints < 1) {
+        fail("mst_remove_fs_max_frames: joints %d < 1", joints);
+        return -1;
+    }
+    return kFeetMaxFrames;
+}
+// a, b, c, d, e of the reference's second-order recursion (bvh_utils.py:1889-1898), in double, with its literals
+static void butterworth_coefficients(double cutoff, double* k) {
+    const double rate = 1.0 / (1.0 / 20);
+    const double pi = 3.14159265358979;
+    const double wc = tan(cutoff * pi / rate);
+    const double k1 = 1.414213562 * wc;
+    const double k2 = wc * wc;
+    const double a = k2 / (1 + k1 + k2);
+    const double b = 2 * a;
+    const double k3 = b / k2;
+    k[0] = a;
+    k[1] = b;
+    k[2] = a;
+    k[3] = -2 * a + k3;
+    k[4] = 1 - (2 * a) - k3;
+}
+extern "C" int mst_remove_fs(const float* glb, const float* ref, int32_t ref_batch, const int32_t* lengths, int32_t batch, int32_t frames,
+                             int32_t joints, const int32_t* foot_ids, int32_t use_vel3, float thr, int32_t use_window,
+                             int32_t force_on_floor, int32_t interp_length, int32_t filter_before, int32_t filter_after, float* out,
+                             int32_t* contacts, float* foot_vels, double* workspace, int64_t workspace_bytes, void* stream) {
+    if (!glb || !foot_ids || batch < 1 || joints < 1 || interp_length < 0) return fail("mst_remove_fs: bad arguments");
+    if (!out && !contacts && !foot_vels) return fail("mst_remove_fs: no output asked for");
+    if (frames < 2) return fail("mst_remove_fs: frames %d < 2 (a one-frame clip has no velocity)", frames);
+    const int max_frames = mst_remove_fs_max_frames(joints);
+    if (frames > max_frames) return fail("mst_remove_fs: frames %d > %d (mst_remove_fs_max_frames)", frames, max_frames);
+    if (ref && ref_batch != 1 && ref_batch != batch) return fail("mst_remove_fs: reference batch %d is neither 1 nor %d", ref_batch, batch);
+    for (int i = 0; i < 4; i++) {
+        if (foot_ids[i] < 0 || foot_ids[i] >= joints) return fail("mst_remove_fs: foot id %d outside 0..%d", foot_ids[i], joints - 1);
+        for (int j = 0; j < i; j++)
+            if (foot_ids[i] == foot_ids[j]) return fail("mst_remove_fs: duplicate foot id %d", foot_ids[i]);
+    }
+    const int64_t ws_need = (int64_t)sizeof(double) * batch * (frames - 1) * joints * 3;
+    if (out && (filter_before || filter_after) && (!workspace || workspace_bytes < ws_need))
+        return fail("mst_remove_fs: the filter needs a workspace of %lld bytes", (long long)ws_need);
+    FeetArgs p{};
+    p.in = glb;
+    p.out = out;
+    p.ref = ref;
+    p.ref_stride = ref && ref_batch == batch && batch > 1 ? (long long)frames * joints * 3 : 0;
+    p.lengths = lengths;
+    p.T = frames;
+    p.J = joints;
+    for (int i = 0; i < 4; i++) p.fid[i] = foot_ids[i];
+    p.vel3 = use_vel3 != 0;
+    p.use_window = use_window != 0;
+    p.force_on_floor = force_on_floor != 0;
+    p.interp_length = interp_length;
+    p.filter_before = filter_before != 0;
+    p.filter_after = filter_after != 0;
+    p.thr = thr;
+    butterworth_coefficients(3, p.kb);
+    butterworth_coefficients(2.5, p.ka);
+    p.ws = out && (filter_before || filter_after) ? workspace : nullptr;
+    p.contacts = contacts;
+    p.foot_vels = foot_vels;
+    hipLaunchKernelGGL(k_remove_fs, dim3(batch), dim3(256), (size_t)8 * frames, (hipStream_t)stream, p);
     HIPCHECK(hipGetLastError());
     return 0;
 }

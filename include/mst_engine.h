@@ -451,6 +451,32 @@ int mst_recover_from_ric(const float* sample_dev, const float* mean_dev, const f
  * so this is min(4096, shared memory per block / 20 bytes); longer clips are refused on the host.  -1 when the device cannot be asked. */
 int mst_recover_max_frames(void);
 
+/* -------------------------------------------------------------------------------------------
+ * Foot-skate cleanup of joint clips, one launch, one workgroup per clip: the reference's remove_fs
+ * (data_loaders/humanml/common/bvh_utils.py:1685-1809) with get_foot_contact_by_vel_acc (:1591-1639, use_vel3 = 0; thr is its
+ * 0.003, use_window its window refinement), get_foot_contact_by_vel3 (:1642-1682, use_vel3 != 0) and Butterworth (:1872-1916;
+ * filter_before = use_butterworth, cut-off 3; filter_after = after_butterworth, cut-off 2.5; dt = 1/20).  What
+ * sample/demo_style_transfer.py:310-313 does to every clip it writes is two calls of this.
+ * glb_dev: [batch][frames][joints][3] float32 (mst_recover_from_ric's output); out_dev: the same shape, may be glb_dev; NULL: only the
+ * contacts and velocities are computed.
+ * ref_dev: [ref_batch][frames][joints][3], ref_batch 1 or batch, the motion the contacts are detected on; NULL: the clip itself as it
+ * is on entry.  It must not overlap out_dev.  lengths_dev: [batch] int32, 2 <= len <= frames, or NULL (every clip `frames` long):
+ * every stage sees frames 0 .. len-1 only, later frames are copied through.  foot_ids_host: four distinct joint indices, host memory.
+ * contacts_dev: [batch][frames][4] int32 or NULL; foot_vels_dev: [batch][frames-1][4] float32 or NULL (speeds for vel3, y-velocities
+ * otherwise; zero from len-1 on).  workspace_dev: 8 * batch * (frames-1) * joints * 3 bytes when a filter is on, else unused.
+ * The caller is trusted for the shapes and for the VALUES of lengths_dev (the kernel clamps them into 2..frames, so no access leaves
+ * the clip); the Python handle checks both.  Refused here: frames < 2 (the reference raises IndexError), frames above
+ * mst_remove_fs_max_frames, duplicate or out-of-range foot ids, a filter without its workspace.
+ * ----------------------------------------------------------------------------------------- */
+int mst_remove_fs(const float* glb_dev, const float* ref_dev, int32_t ref_batch, const int32_t* lengths_dev, int32_t batch,
+                  int32_t frames, int32_t joints, const int32_t* foot_ids_host, int32_t use_vel3, float thr, int32_t use_window,
+                  int32_t force_on_floor, int32_t interp_length, int32_t filter_before, int32_t filter_after, float* out_dev,
+                  int32_t* contacts_dev, float* foot_vels_dev, double* workspace_dev, int64_t workspace_bytes, void* stream);
+/* Longest clip mst_remove_fs takes at this joint count: never below mst_recover_max_frames, so that whatever mst_recover_from_ric returns
+ * can be cleaned.  The kernel keeps two byte maps of 4 * frames contacts in LDS (32 KB at the cap of 4096) and the filter's forward
+ * result in the caller's workspace, so today the bound is the same for every joint count.  -1 for joints < 1. */
+int mst_remove_fs_max_frames(int32_t joints);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
