@@ -30,6 +30,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_small.h"
 #include "mst_style.h"
 #include "mst_feet.h"
+#include "mst_ik.h"
 
 using namespace mst;
 
@@ -3197,6 +3198,79 @@ extern "C" int mst_remove_fs(const float* glb, const float* ref, int32_t ref_bat
     p.contacts = contacts;
     p.foot_vels = foot_vels;
     hipLaunchKernelGGL(k_remove_fs, dim3(batch), dim3(256), (size_t)8 * frames, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// Joint-rotation fit (mst_ik.h).  k_ik_solve keeps a lane's parameters, both Adam moments and its target in LDS, [slot][64 lanes]; the
+// joint count is bounded by that, the clip length by the three rows k_ik_init keeps for the running sums (48 KB at the cap, which
+// every device gives a workgroup without an opt-in: the bound needs no device to be asked).
+extern "C" int mst_fit_joints_max_joints(void) { return kIkMaxJoints; }
+extern "C" int mst_fit_joints_max_frames(int32_t joints) {
+    if (joints < 2 || joints > kIkMaxJoints) {
+        fail("mst_fit_joints_max_frames: joints %d outside 2..%d", joints, kIkMaxJoints);
+        return -1;
+    }
+    return kIkMaxFrames;
+}
+extern "C" int mst_fit_joints(const float* data, int64_t stride_batch, int64_t stride_frame, int64_t stride_feat, const float* mean,
+                              const float* stdv, const float* target, const int32_t* lengths, int32_t batch, int32_t frames,
+                              int32_t feats, int32_t joints, const int32_t* parents, const float* offsets, int32_t iters,
+                              int32_t true_gradient, float* cont6d, float* r_pos, float* r_rot_quat, float* positions,
+                              float* joint_quats, float* frame_loss, float* grad, void* stream) {
+    if (joints < 2 || joints > kIkMaxJoints) return fail("mst_fit_joints: joints %d outside 2..%d (mst_fit_joints_max_joints)", joints, kIkMaxJoints);
+    if (iters < 1) return fail("mst_fit_joints: iters %d < 1", iters);
+    if (feats != 9 * joints + 1) return fail("mst_fit_joints: feats %d != 9 * %d + 1 (the position-rotation vector)", feats, joints);
+    if (frames < 1) return fail("mst_fit_joints: frames %d < 1", frames);
+    if (batch < 1) return fail("mst_fit_joints: batch %d < 1", batch);
+    if (!parents || !offsets) return fail("mst_fit_joints: null skeleton");
+    for (int j = 1; j < joints; j++)
+        if (parents[j] < 0 || parents[j] >= j)
+            return fail("mst_fit_joints: parents[%d] = %d: not a tree rooted at 0 with parents[j] < j", j, parents[j]);
+    if (!data || !target || !cont6d || !r_pos || !r_rot_quat || !positions || !joint_quats) return fail("mst_fit_joints: null argument");
+    if ((mean == nullptr) != (stdv == nullptr)) return fail("mst_fit_joints: mean and std come together");
+    const int max_frames = mst_fit_joints_max_frames(joints);
+    if (max_frames < 0) return 1;
+    if (frames > max_frames) return fail("mst_fit_joints: frames %d > %d (mst_fit_joints_max_frames)", frames, max_frames);
+    int dev = 0, lds = 0;
+    HIPCHECK(hipGetDevice(&dev));
+    HIPCHECK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    const size_t solve_lds = sizeof(float) * kIkLanes * (21 * (size_t)joints + 21);
+    if (solve_lds > (size_t)lds) return fail("mst_fit_joints: %d joints need %zu bytes of LDS, the device gives a workgroup %d", joints, solve_lds, lds);
+    IkArgs p{};
+    p.data = data;
+    p.sb = stride_batch;
+    p.st = stride_frame;
+    p.sf = stride_feat;
+    p.mean = mean;
+    p.stdv = stdv;
+    p.target = target;
+    p.lengths = lengths;
+    p.B = batch;
+    p.T = frames;
+    p.J = joints;
+    p.iters = iters;
+    p.true_gradient = true_gradient != 0;
+    for (int j = 0; j < joints; j++) p.leaf[j] = 1;
+    for (int j = 0; j < joints; j++) {
+        p.parents[j] = j ? parents[j] : 0;
+        if (j) p.leaf[parents[j]] = 0;
+        for (int k = 0; k < 3; k++) p.off[j][k] = offsets[3 * j + k];
+    }
+    p.cont6d = cont6d;
+    p.r_pos = r_pos;
+    p.r_rot = r_rot_quat;
+    p.positions = positions;
+    p.quats = joint_quats;
+    p.frame_loss = frame_loss;
+    p.grad = grad;
+    const size_t init_lds = sizeof(float) * 3 * frames;      // at most 48 KB: below the opt-in threshold
+    hipLaunchKernelGGL(k_ik_init, dim3(batch), dim3(256), init_lds, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    if (solve_lds > 64 * 1024)
+        CHECK(ensure_dyn_lds((const void*)k_ik_solve, (int)(sizeof(float) * kIkLanes * (21 * kIkMaxJoints + 21))));
+    const long long lanes = (long long)batch * frames;
+    hipLaunchKernelGGL(k_ik_solve, dim3((unsigned)((lanes + kIkLanes - 1) / kIkLanes)), dim3(kIkLanes), solve_lds, (hipStream_t)stream, p);
     HIPCHECK(hipGetLastError());
     return 0;
 }

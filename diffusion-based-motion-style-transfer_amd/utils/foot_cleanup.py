@@ -183,19 +183,20 @@ def remove_fs(output_path, glb_motion, ref_motion, bonenames, ee_names, interp_l
 
 
 def clean_joints(sample, mean, std, joints_num, ee_ids, ref_joints=None, lengths=None, passes=2, vel3_thr=0.05, interp_length=5,
-                 force_on_floor=True, after_butterworth=True):
+                 force_on_floor=True, after_butterworth=True, *, _lengths_checked=False):
     """`recover_joints` followed by the demo's passes (sample/demo_style_transfer.py:310-313; the defaults are the demo's settings):
     pass 1 detects contacts on `ref_joints` ([B or 1, T, J, 3], the content motion; None: the clip itself), later passes on the clip
     itself.  sample: [B, F, 1, T] normalised hml_vec CUDA tensor; lengths: [B].  -> joints [B, T, J, 3].
     Every launch is enqueued on the caller's current stream, with no host copy or synchronisation between them (lengths are checked,
-    and a host array of them uploaded, before the first)."""
+    and a host array of them uploaded, before the first; `_lengths_checked`: the caller, joint_fit.fit_clean_joints, has done that and
+    passes the device tensor)."""
     if not sample.is_cuda:
         raise RuntimeError(_NO_CPU.format("clean_joints"))
     B, T = sample.shape[0], sample.shape[-1]
     if ref_joints is not None and ref_joints.dim() == 5:
         ref_joints = ref_joints[:, 0]                       # recover_joints's own layout
     ids = _validate("clean_joints", (B, T, joints_num, 3), ref_joints, ee_ids)
-    ld = _checked_lengths(lengths, B, T, sample.device)
+    ld = lengths if _lengths_checked else _checked_lengths(lengths, B, T, sample.device)
     _need_cuda("clean_joints", ref_joints)
     joints = recover_joints(sample, mean, std, joints_num)[:, 0]
     ref = None if ref_joints is None else _f32(ref_joints)

@@ -1,0 +1,255 @@
+"""Joint rotations fitted to joint positions on the GPU: the counterpart of `fit_joints_bvh` (data_loaders/humanml/common/bvh_utils.py:
+1811-1846), the last numeric stage of sample/demo_style_transfer.py (:217, :306, :318).  The reference runs `iter_num` Adam steps of torch
+autograd through `InverseKinematics_hmlvec` (common/Kinematics.py:30-91) and `Skeleton.forward_kinematics_real_cont6d`
+(common/skeleton.py:200-222); here every frame's 6 J + 7 parameters are optimised in one lane of one launch (csrc/mst_ik.h), after one
+launch for the starting point.  `fit_clean_joints` is demo lines 310-318 for a batch: `clean_joints`, then the fit of the same sample to
+the cleaned positions, without the clip leaving the GPU.
+
+The reference's gradient on the first three 6D components of every joint is not the true one: its forward pass builds the local positions
+in the storage autograd saved as x_raw, so the backward of x_raw / |x_raw| reads the joint's offset (for the root: the frame's r_pos) in
+x_raw's place.  Its results are what parity means here, so that is the default; `true_gradient=True` gives the true gradient.
+
+Left out: `use_lbfgs` (no caller), `iter_num=None` (the reference's `while loss > 2e-5` never updates `loss` and never ends), BVH text
+writing (the reference's `Anim` / `save_bvh` are used when a checkout is importable), and `rotm2axangle`'s SVD branch for a rotation whose
+angle is an exact multiple of pi (common/rotation.py:467-472): such a joint gets the plain formula's result."""
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .. import _native as N
+from . import foot_cleanup as fc
+
+_NO_CPU = fc._NO_CPU
+FRAME_TIME = 1 / 20
+
+
+@dataclass
+class JointFit:
+    """What `fit_joints` returns.  cont6d [B, T, J, 6], r_pos [B, T, 3] and r_rot_quat [B, T, 4] are the optimised parameters (the
+    quaternion as optimised, not normalised); positions [B, T, J, 3] their forward kinematics; joint_quats [B, T, J, 4] what the reference
+    writes to the animation (`cont6d2q`, the root joint multiplied by the normalised r_rot_quat).  frame_loss [B, T, 2]: the loss of the
+    first and of the last iteration per frame, each before its update (summed over frames: what `step()` returns); grad [B, T, 6 J + 7]:
+    the gradient of the last iteration, laid out cont6d, r_pos, r_rot_quat.  Both are None unless asked for, and zero for frames at or
+    beyond a clip's length."""
+    cont6d: torch.Tensor
+    r_pos: torch.Tensor
+    r_rot_quat: torch.Tensor
+    positions: torch.Tensor
+    joint_quats: torch.Tensor
+    frame_loss: Optional[torch.Tensor] = None
+    grad: Optional[torch.Tensor] = None
+
+
+def max_joints():
+    """Most joints `fit_joints` takes (mst_fit_joints_max_joints)."""
+    return int(N.lib().mst_fit_joints_max_joints())
+
+
+def max_frames(joints):
+    """Longest clip `fit_joints` takes at this joint count (mst_fit_joints_max_frames)."""
+    n = int(N.lib().mst_fit_joints_max_frames(int(joints)))
+    if n < 0:
+        N.check(1)
+    return n
+
+
+def parents_from_chains(chains, joints):
+    """common/skeleton.py:11-15: a joint's parent is its predecessor in its kinematic chain; joints no chain names hang off the root."""
+    parents = [0] * joints
+    parents[0] = -1
+    for chain in chains:
+        for k in range(1, len(chain)):
+            if not 0 <= int(chain[k]) < joints:
+                raise ValueError(f"fit_joints: joint {chain[k]} of a kinematic chain is outside 0..{joints - 1}")
+            parents[int(chain[k])] = int(chain[k - 1])
+    return parents
+
+
+def _resolve_parents(parents, J):
+    """A parents list, a list of kinematic chains, or an object with `_parents` (the reference's Skeleton) -> list of J ints, checked to
+    be a tree rooted at joint 0 in which every joint comes after its parent."""
+    if hasattr(parents, "_parents"):
+        parents = parents._parents
+    parents = list(parents)
+    if parents and isinstance(parents[0], (list, tuple, np.ndarray)):
+        parents = parents_from_chains(parents, J)
+    parents = [int(a) for a in parents]
+    if len(parents) != J:
+        raise ValueError(f"fit_joints: {len(parents)} parents for {J} joints")
+    for j in range(1, J):
+        if not 0 <= parents[j] < j:
+            raise ValueError(f"fit_joints: parents[{j}] = {parents[j]}: not a tree rooted at joint 0 with parents[j] < j")
+    return parents
+
+
+def _checked_lengths(lengths, B, T, device):
+    """-> int32 device tensor [B] or None.  Checked on the host (a CUDA tensor is copied back once for it): 1 <= len <= T."""
+    if lengths is None:
+        return None
+    host = lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)
+    host = host.reshape(-1).astype(np.int64)
+    if host.shape[0] != B:
+        raise ValueError(f"fit_joints: {host.shape[0]} lengths for {B} clips")
+    if host.min() < 1 or host.max() > T:
+        raise ValueError(f"fit_joints: lengths {host.min()}..{host.max()} outside 1..{T}")
+    if torch.is_tensor(lengths) and lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous():
+        return lengths
+    return torch.from_numpy(host.astype(np.int32)).to(device)
+
+
+def _validate(what, data_shape, glb_shape, J, parents, real_offset, iter_num, mean, std):
+    """Everything that can be refused without a GPU.  -> (B, T, F, sampler layout?, parents, offsets [J, 3] float32)."""
+    J = int(J)
+    limit = max_joints()
+    if J < 2 or J > limit:
+        raise ValueError(f"{what}: {J} joints outside 2..{limit} (mst_fit_joints_max_joints)")
+    if iter_num is None:
+        raise ValueError(f"{what}: iter_num=None is the reference's `while loss > 2e-5`, which never updates `loss` and never ends; "
+                         "name a number of iterations")
+    if int(iter_num) < 1:
+        raise ValueError(f"{what}: iter_num {iter_num} < 1")
+    parents = _resolve_parents(parents, J)
+    off = np.ascontiguousarray(np.asarray(real_offset, dtype=np.float32))
+    if off.shape != (J, 3):
+        raise ValueError(f"{what}: offsets of shape {off.shape}, expected ({J}, 3)")
+    F = 9 * J + 1
+    if len(data_shape) == 3:
+        B, T, feats = data_shape
+        sampler = False
+    elif len(data_shape) == 4 and data_shape[2] == 1:
+        B, feats, _, T = data_shape
+        sampler = True
+    else:
+        raise ValueError(f"{what}: data of shape {tuple(data_shape)}, expected [B, T, {F}] or the samplers' [B, {F}, 1, T]")
+    if feats != F:
+        raise ValueError(f"{what}: {feats} features, expected 9 * {J} + 1 = {F} (the position-rotation vector; the 263-feature HumanML "
+                         "vector has no such reshape, and the demo skips it)")
+    if tuple(glb_shape) != (B, T, J, 3):
+        raise ValueError(f"{what}: target of shape {tuple(glb_shape)}, expected [{B}, {T}, {J}, 3]")
+    if (mean is None) != (std is None):
+        raise ValueError(f"{what}: mean and std come together")
+    for name, v in (("mean", mean), ("std", std)):
+        if v is not None and tuple(np.shape(v)) != (F,):
+            raise ValueError(f"{what}: {name} of shape {tuple(np.shape(v))}, expected ({F},)")
+    if T < 1 or B < 1:
+        raise ValueError(f"{what}: {B} clips of {T} frames")
+    frames = max_frames(J)
+    if T > frames:
+        raise RuntimeError(f"{what}: {T} frames > {frames}, the longest clip mst_fit_joints takes (mst_fit_joints_max_frames({J}))")
+    return B, T, F, sampler, parents, off
+
+
+def _stat(v, device):
+    t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float32))
+    return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _fit_tensors(data, sampler, glb, J, parents, off, iters, ld, true_gradient, mean, std, return_loss, return_grad):
+    """The two launches, on the current stream of data's device.  data: fp32 CUDA tensor of either layout, any strides; glb: contiguous
+    fp32 [B, T, J, 3]; ld: checked lengths on the device or None."""
+    dev = data.device
+    if sampler:
+        B, F, _, T = data.shape
+        sb, sf, st = data.stride(0), data.stride(1), data.stride(3)
+    else:
+        B, T, F = data.shape
+        sb, st, sf = data.stride()
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    res = JointFit(new(B, T, J, 6), new(B, T, 3), new(B, T, 4), new(B, T, J, 3), new(B, T, J, 4),
+                   new(B, T, 2) if return_loss else None, new(B, T, 6 * J + 7) if return_grad else None)
+    m = None if mean is None else _stat(mean, dev)           # named: they must outlive the launch
+    s = None if std is None else _stat(std, dev)
+    par = (C.c_int32 * J)(*parents)
+    offs = (C.c_float * (3 * J))(*off.reshape(-1).tolist())
+    with torch.cuda.device(dev):
+        N.check(N.lib().mst_fit_joints(N.ptr(data), sb, st, sf, N.ptr(m), N.ptr(s), N.ptr(glb), N.ptr(ld), B, T, F, J, par, offs, int(iters),
+                                       int(bool(true_gradient)), N.ptr(res.cont6d), N.ptr(res.r_pos), N.ptr(res.r_rot_quat),
+                                       N.ptr(res.positions), N.ptr(res.joint_quats), N.ptr(res.frame_loss), N.ptr(res.grad),
+                                       N.stream_ptr(dev)))
+    return res
+
+
+def fit_joints(initial_data, joint_num, parents, real_offset, glb, iter_num=100, *, lengths=None, true_gradient=False, mean=None, std=None,
+               return_loss=False, return_grad=False):
+    """`iter_num` Adam steps (lr 1e-3, betas 0.9 / 0.999, eps 1e-8) on every frame's 6D joint rotations, root position and root quaternion
+    so that their forward kinematics meets `glb`, under the reference's Geman-McClure loss at sigma 100.  -> JointFit.
+
+    initial_data: the position-rotation vector, 9 J + 1 features a frame -- [B, T, 9J+1] denormalised, or the samplers' [B, 9J+1, 1, T]
+    output together with `mean` / `std` ([9J+1]; the kernel denormalises as it reads).  Any strides; it is not modified (the reference
+    steps a view of its input in place).  glb: [B, T, J, 3], the positions to fit.  parents: a parents list, a list of kinematic chains,
+    or an object with `_parents` such as the reference's Skeleton.  real_offset: [J, 3]; row 0 is ignored, as in the reference.
+    lengths: [B]; frames at or beyond a clip's length take no step.  true_gradient: see the module docstring."""
+    if not torch.is_tensor(initial_data) or not torch.is_tensor(glb):
+        raise TypeError("fit_joints: initial_data and glb are tensors (fit_joints_bvh takes the reference's numpy target)")
+    B, T, F, sampler, parents, off = _validate("fit_joints", initial_data.shape, glb.shape, joint_num, parents, real_offset, iter_num, mean, std)
+    ld = _checked_lengths(lengths, B, T, initial_data.device)
+    fc._need_cuda("fit_joints", initial_data, glb, ld)
+    data = initial_data.detach().to(torch.float32)
+    target = glb.detach().to(torch.float32).contiguous()
+    return _fit_tensors(data, sampler, target, int(joint_num), parents, off, iter_num, ld, true_gradient, mean, std, return_loss, return_grad)
+
+
+def _reference_save(path, joint_quats, positions, real_offset, parents, names, frametime):
+    from data_loaders.humanml.common.bvh_utils import Anim, save_bvh
+    save_bvh(path, Anim(joint_quats, positions, real_offset, parents, names), frametime)
+
+
+def _default_save():
+    try:
+        from data_loaders.humanml.common.bvh_utils import Anim, save_bvh  # noqa: F401
+    except ImportError as e:
+        raise ImportError("fit_joints_bvh: `Anim` and `save_bvh` of data_loaders.humanml.common.bvh_utils cannot be imported (no reference "
+                          "checkout on the path?); BVH writing is not reimplemented here -- pass save=callable(path, joint_quats, positions, "
+                          "real_offset, parents, names, frametime)") from e
+    return _reference_save
+
+
+def fit_joints_bvh(path, initial_data, joint_num, skeleton, real_offset, glb, names=None, use_lbfgs=False, iter_num=100, *, save=None):
+    """The reference's `fit_joints_bvh`, signature and defaults: fit the clip's rotations to `glb` and write the animation.
+    initial_data: [T, 9J+1] tensor or array; glb: [T, J, 3] numpy array; skeleton: anything `fit_joints` takes as parents.
+    `save(path, joint_quats [T, J, 4], positions [T, J, 3], real_offset [J, 3], parents, names, 1 / 20)` receives what the reference hands
+    to `Anim` and `save_bvh` -- the offsets with row 0 zeroed, the positions those offsets with r_pos in row 0 of every frame -- and
+    defaults to exactly those two, imported from a reference checkout.  -> the JointFit."""
+    if use_lbfgs:
+        raise NotImplementedError("fit_joints_bvh: use_lbfgs is not implemented (no caller uses it)")
+    data = initial_data if torch.is_tensor(initial_data) else torch.as_tensor(np.asarray(initial_data, dtype=np.float32))
+    target = torch.as_tensor(np.asarray(glb, dtype=np.float32))
+    if data.dim() != 2 or target.dim() != 3:
+        raise ValueError(f"fit_joints_bvh: data of shape {tuple(data.shape)} and target of shape {tuple(target.shape)}, expected [T, F] and [T, J, 3]")
+    _, _, _, _, parents, off = _validate("fit_joints_bvh", data[None].shape, target[None].shape, joint_num, skeleton, real_offset, iter_num,
+                                         None, None)
+    save = _default_save() if save is None else save
+    if not data.is_cuda and torch.cuda.is_available():
+        data = data.cuda()
+    if not data.is_cuda:
+        raise RuntimeError(_NO_CPU.format("fit_joints_bvh"))
+    fit = fit_joints(data[None], joint_num, parents, off, target.to(data.device)[None], iter_num)
+    real_offset = off.copy()
+    real_offset[0, :] = 0
+    positions = np.repeat(real_offset[None], data.shape[0], axis=0)
+    positions[:, 0, :] = fit.r_pos[0].cpu().numpy()
+    save(path, fit.joint_quats[0].cpu().numpy(), positions, real_offset, parents, names, FRAME_TIME)
+    return fit
+
+
+def fit_clean_joints(sample, mean, std, joints_num, parents, real_offset, ee_ids, ref_joints=None, lengths=None, iter_num=100, *,
+                     true_gradient=False, return_loss=False, return_grad=False, **clean):
+    """sample/demo_style_transfer.py:310-318 for a batch: `clean_joints` (recover_from_ric and the foot-skate passes; `clean` takes its
+    keywords), then `fit_joints` of the same sample to the cleaned positions.  sample: [B, 9J+1, 1, T] normalised CUDA tensor.
+    -> (joints [B, T, J, 3], JointFit).  Every launch is enqueued on the caller's current stream with no host copy or synchronisation in
+    between (lengths are checked, and a host array of them uploaded, before the first)."""
+    if not torch.is_tensor(sample) or sample.dim() != 4:
+        raise ValueError("fit_clean_joints: sample is the samplers' [B, F, 1, T] tensor")
+    B, T = sample.shape[0], sample.shape[-1]
+    _, _, _, _, parents, off = _validate("fit_clean_joints", sample.shape, (B, T, int(joints_num), 3), joints_num, parents, real_offset,
+                                         iter_num, mean, std)
+    if not sample.is_cuda:
+        raise RuntimeError(_NO_CPU.format("fit_clean_joints"))
+    ld = None if lengths is None else fc._checked_lengths(lengths, B, T, sample.device)
+    joints = fc.clean_joints(sample, mean, std, joints_num, ee_ids, ref_joints=ref_joints, lengths=ld, _lengths_checked=True, **clean)
+    data = sample.detach().to(torch.float32)
+    fit = _fit_tensors(data, True, joints, int(joints_num), parents, off, iter_num, ld, true_gradient, mean, std, return_loss, return_grad)
+    return joints, fit

@@ -477,6 +477,40 @@ int mst_remove_fs(const float* glb_dev, const float* ref_dev, int32_t ref_batch,
  * result in the caller's workspace, so today the bound is the same for every joint count.  -1 for joints < 1. */
 int mst_remove_fs_max_frames(int32_t joints);
 
+/* -------------------------------------------------------------------------------------------
+ * Joint rotations fitted to joint positions, two launches: the optimisation inside the reference's fit_joints_bvh
+ * (data_loaders/humanml/common/bvh_utils.py:1811-1846) -- InverseKinematics_hmlvec (common/Kinematics.py:30-91; the starting point is
+ * recover_root_rot_pos_this, :8-27) stepping torch.optim.Adam (lr 1e-3, betas 0.9 / 0.999, eps 1e-8) `iters` times through
+ * Skeleton.forward_kinematics_real_cont6d (common/skeleton.py:200-222) under the Geman-McClure loss at sigma 100 -- and the conversion
+ * that follows it (cont6d2q, common/rotation.py:744-776; the root joint times the normalised r_rot_quat).  Every frame is an
+ * optimisation of its own (6 * joints + 7 parameters) and runs in one lane from its first iteration to its last.
+ * data_dev: the position-rotation vector, feats = 9 * joints + 1 per frame, element (b, t, f) at
+ * data_dev[b * stride_batch + t * stride_frame + f * stride_feat] (strides in elements: [batch][frames][feats] is (frames * feats,
+ * feats, 1); the samplers' [batch][feats][1][frames] is (feats * frames, 1, frames)); mean_dev / std_dev: [feats], both or neither,
+ * applied as x * std + mean.  target_dev: [batch][frames][joints][3], the positions to fit.  lengths_dev: [batch] int32 or NULL;
+ * frames at or beyond a clip's length take no step (their outputs are those of the starting point, their loss and gradient zero).
+ * parents_host: [joints], parents[0] ignored, 0 <= parents[j] < j; offsets_host: [joints][3], row 0 ignored.
+ * Outputs: cont6d_dev [batch][frames][joints][6], r_pos_dev [batch][frames][3], r_rot_quat_dev [batch][frames][4] (as optimised, not
+ * normalised), positions_dev [batch][frames][joints][3] (forward kinematics of the fit), joint_quats_dev [batch][frames][joints][4];
+ * optional (NULL: not written) frame_loss_dev [batch][frames][2], the loss of the first and of the last iteration, each before its
+ * update, and grad_dev [batch][frames][6 * joints + 7], the gradient of the last iteration (cont6d, r_pos, r_rot_quat).
+ * The quirk: the reference builds its local positions in the storage autograd saved as x_raw for the backward of x_raw / |x_raw|, so
+ * its gradient on the first three 6D components is g / n - s (g . s) / n^3 with s the joint's offset (for the root: the frame's r_pos)
+ * where the true gradient has x_raw.  true_gradient = 0 reproduces the reference, != 0 gives the true gradient.
+ * Refused here: joints < 2 or above mst_fit_joints_max_joints, a parents array that is not a tree rooted at 0 with parents[j] < j,
+ * iters < 1, feats != 9 * joints + 1, frames < 1 or above mst_fit_joints_max_frames, one of mean / std without the other.
+ * ----------------------------------------------------------------------------------------- */
+int mst_fit_joints(const float* data_dev, int64_t stride_batch, int64_t stride_frame, int64_t stride_feat, const float* mean_dev,
+                   const float* std_dev, const float* target_dev, const int32_t* lengths_dev, int32_t batch, int32_t frames,
+                   int32_t feats, int32_t joints, const int32_t* parents_host, const float* offsets_host, int32_t iters,
+                   int32_t true_gradient, float* cont6d_dev, float* r_pos_dev, float* r_rot_quat_dev, float* positions_dev,
+                   float* joint_quats_dev, float* frame_loss_dev, float* grad_dev, void* stream);
+/* Most joints mst_fit_joints takes: a 64-lane workgroup keeps 21 * joints + 21 floats a lane in LDS (24 joints: 134 400 bytes). */
+int mst_fit_joints_max_joints(void);
+/* Longest clip mst_fit_joints takes: the starting point's three running sums keep three fp32 rows of `frames` entries in LDS, 48 KB at
+ * the cap of 4096, the same for every joint count.  -1 for joints outside 2 .. mst_fit_joints_max_joints. */
+int mst_fit_joints_max_frames(int32_t joints);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
