@@ -31,6 +31,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_style.h"
 #include "mst_feet.h"
 #include "mst_ik.h"
+#include "mst_encode.h"
 
 using namespace mst;
 
@@ -3271,6 +3272,93 @@ extern "C" int mst_fit_joints(const float* data, int64_t stride_batch, int64_t s
         CHECK(ensure_dyn_lds((const void*)k_ik_solve, (int)(sizeof(float) * kIkLanes * (21 * kIkMaxJoints + 21))));
     const long long lanes = (long long)batch * frames;
     hipLaunchKernelGGL(k_ik_solve, dim3((unsigned)((lanes + kIkLanes - 1) / kIkLanes)), dim3(kIkLanes), solve_lds, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// Motion encoder (mst_encode.h).  k_encode keeps two fp32 rows of the per-frame forward direction and one root quaternion a frame in
+// LDS, 24 bytes a frame whatever the joint count or the mode: 48 KB at the cap, which every device gives a workgroup without an opt-in.
+extern "C" int mst_encode_max_frames(int32_t joints, int32_t mode) {
+    if (joints < 2 || joints > kEncMaxJoints || (mode != kEncPosRot && mode != kEncHml)) {
+        fail("mst_encode_max_frames: joints %d outside 2..%d or mode %d neither 0 (POSROT) nor 1 (HML)", joints, kEncMaxJoints, mode);
+        return -1;
+    }
+    return kEncMaxFrames;
+}
+extern "C" int mst_encode_motion(const float* positions, const float* rotations, const int32_t* lengths, const float* mean, const float* stdv,
+                                 int32_t batch, int32_t frames, int32_t joints, int32_t mode, const int32_t* face_ids,
+                                 const int32_t* foot_ids, const int32_t* chains, const int32_t* chain_starts, int32_t num_chains,
+                                 const float* raw_offsets, float feet_thre, int32_t frames_out, float* sample, int32_t* lengths_out,
+                                 float* global_positions, float* local_positions, float* l_velocity, void* stream) {
+    if (mode != kEncPosRot && mode != kEncHml) return fail("mst_encode_motion: mode %d is neither 0 (POSROT) nor 1 (HML)", mode);
+    if (joints < 2 || joints > kEncMaxJoints) return fail("mst_encode_motion: joints %d outside 2..%d", joints, kEncMaxJoints);
+    if (batch < 1) return fail("mst_encode_motion: batch %d < 1", batch);
+    if (frames < 2) return fail("mst_encode_motion: frames %d < 2 (a one-frame clip has no velocity row)", frames);
+    if (frames_out < 1) return fail("mst_encode_motion: frames_out %d < 1", frames_out);
+    const int max_frames = mst_encode_max_frames(joints, mode);
+    if (frames > max_frames) return fail("mst_encode_motion: frames %d > %d (mst_encode_max_frames)", frames, max_frames);
+    if (!positions || !sample || !lengths_out || !face_ids) return fail("mst_encode_motion: null argument");
+    if (mode == kEncPosRot && !rotations) return fail("mst_encode_motion: POSROT needs the rotations");
+    if ((mean == nullptr) != (stdv == nullptr)) return fail("mst_encode_motion: mean and std come together");
+    for (int i = 0; i < 4; i++) {
+        if (face_ids[i] < 0 || face_ids[i] >= joints) return fail("mst_encode_motion: face joint %d outside 0..%d", face_ids[i], joints - 1);
+        for (int j = 0; j < i; j++)
+            if (face_ids[i] == face_ids[j]) return fail("mst_encode_motion: duplicate face joint %d", face_ids[i]);
+    }
+    if (mode == kEncHml && (!foot_ids || !chains || !chain_starts || num_chains < 1 || !raw_offsets))
+        return fail("mst_encode_motion: HML needs foot ids, kinematic chains and raw offsets");
+    EncArgs p{};
+    if (foot_ids)
+        for (int i = 0; i < 4; i++) {
+            if (foot_ids[i] < 0 || foot_ids[i] >= joints) return fail("mst_encode_motion: foot joint %d outside 0..%d", foot_ids[i], joints - 1);
+            p.fid[i] = foot_ids[i];
+        }
+    if (chains && chain_starts && num_chains > 0) {
+        bool placed[kEncMaxJoints] = {true};
+        for (int c = 0; c < num_chains; c++) {
+            const int lo = chain_starts[c], hi = chain_starts[c + 1];
+            if (lo < 0 || hi <= lo) return fail("mst_encode_motion: chain %d is empty", c);
+            for (int k = lo; k < hi; k++)
+                if (chains[k] < 0 || chains[k] >= joints) return fail("mst_encode_motion: joint %d of chain %d outside 0..%d", chains[k], c, joints - 1);
+            if (!placed[chains[lo]]) return fail("mst_encode_motion: chain %d starts at joint %d, which no earlier chain has placed", c, chains[lo]);
+            for (int k = lo + 1; k < hi; k++) {
+                if (placed[chains[k]]) return fail("mst_encode_motion: joint %d is named twice as a child (chain %d)", chains[k], c);
+                placed[chains[k]] = true;
+                p.link_child[p.n_links] = chains[k];
+                p.link_parent[p.n_links] = chains[k - 1];
+                p.link_first[p.n_links] = k == lo + 1;
+                p.named[chains[k]] = 1;
+                p.n_links++;
+            }
+        }
+    }
+    if (raw_offsets)
+        for (int j = 0; j < joints; j++)
+            for (int k = 0; k < 3; k++) p.raw[j][k] = raw_offsets[3 * j + k];
+    {   // scipy.ndimage._gaussian_kernel1d(sigma 20, order 0, radius 80), in double
+        double sum = 0.0;
+        for (int k = -kEncRadius; k <= kEncRadius; k++) sum += exp(-0.5 / (20.0 * 20.0) * (double)(k * k));
+        for (int k = 0; k <= kEncRadius; k++) p.taps[k] = exp(-0.5 / (20.0 * 20.0) * (double)(k * k)) / sum;
+    }
+    p.pos = positions;
+    p.rot = rotations;
+    p.lengths = lengths;
+    p.mean = mean;
+    p.stdv = stdv;
+    p.B = batch;
+    p.T = frames;
+    p.J = joints;
+    p.mode = mode;
+    p.frames_out = frames_out;
+    p.feats = mode == kEncPosRot ? 9 * joints + 1 : 12 * joints - 1;
+    p.feet_thre = feet_thre;
+    for (int i = 0; i < 4; i++) p.face[i] = face_ids[i];
+    p.sample = sample;
+    p.out_len = lengths_out;
+    p.glob = global_positions;
+    p.local = local_positions;
+    p.lvel = l_velocity;
+    hipLaunchKernelGGL(k_encode, dim3(batch), dim3(kEncThreads), sizeof(float) * 6 * frames, (hipStream_t)stream, p);
     HIPCHECK(hipGetLastError());
     return 0;
 }

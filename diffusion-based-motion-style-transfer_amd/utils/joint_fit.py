@@ -253,3 +253,16 @@ def fit_clean_joints(sample, mean, std, joints_num, parents, real_offset, ee_ids
     data = sample.detach().to(torch.float32)
     fit = _fit_tensors(data, True, joints, int(joints_num), parents, off, iter_num, ld, true_gradient, mean, std, return_loss, return_grad)
     return joints, fit
+
+
+def encode_fit(joints, fit, *, chains, face_joint_indx, fid_l, fid_r, raw_offsets=None, lengths=None, mean=None, std=None, frames_out=None,
+               feet_thre=0.002):
+    """What `fit_clean_joints` returned, back in feature space: `motion_process.encode_joints` of the cleaned joints [B, T, J, 3] and
+    `fit.joint_quats` [B, T, J, 4] in the position-rotation layout the fit read.  -> (sample [B, 9J+1, 1, frames_out], lengths int32 [B]):
+    what `ddim_sample_loop`, `StyleBank` and `ddim_reverse_sample_loop` take as `init_image` and `inpainted_motion`, so a transferred,
+    cleaned and fitted clip can go through another style without leaving the GPU."""
+    from .motion_process import POSROT, encode_joints
+    if not isinstance(fit, JointFit):
+        raise TypeError("encode_fit: fit is the JointFit of fit_joints / fit_clean_joints")
+    return encode_joints(joints, fit.joint_quats, chains=chains, raw_offsets=raw_offsets, face_joint_indx=face_joint_indx, fid_l=fid_l,
+                         fid_r=fid_r, feet_thre=feet_thre, mode=POSROT, lengths=lengths, mean=mean, std=std, frames_out=frames_out)

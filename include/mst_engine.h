@@ -511,6 +511,40 @@ int mst_fit_joints_max_joints(void);
  * the cap of 4096, the same for every joint count.  -1 for joints outside 2 .. mst_fit_joints_max_joints. */
 int mst_fit_joints_max_frames(int32_t joints);
 
+/* -------------------------------------------------------------------------------------------
+ * Joint positions (and rotations) encoded into the model's feature rows, one launch, one workgroup per clip: the reference's
+ * process_file_with_rotation (data_loaders/humanml/common/bvh_utils.py:1091-1287; mode 0, POSROT: 9 * joints + 1 features, the layout
+ * mst_fit_joints reads) and process_file (bvh_utils.py:898-1088; mode 1, HML: 12 * joints - 1 features, 263 at 22 joints), followed by
+ * process_np_motion's z-normalisation and zero padding (data_loaders/humanml/data/dataset.py:484-519).  The stages -- floor, origin,
+ * initial facing (quatbetween, common/rotation.py:97-108), the smoothed root rotation of Skeleton.inverse_kinematics_np
+ * (common/skeleton.py:55-86; gaussian_filter1d at sigma 20, 161 taps summed in double, index clamped into the clip; qbetween,
+ * common/quaternion.py:421-431), in HML the chain IK (skeleton.py:88-103, every chain restarting from the frame's root quaternion),
+ * root velocities, local pose, local velocities and foot contacts -- all run over a clip's own length.
+ * positions_dev: [batch][frames][joints][3] float32; rotations_dev: [batch][frames][joints][4] (w, x, y, z), NULL allowed in HML.  Neither
+ * is written (the reference mutates its arguments).  lengths_dev: [batch] int32, 2 <= len <= frames, or NULL; the kernel clamps the
+ * values into 2..frames, so no access leaves a clip (the Python handle checks them).  mean_dev / std_dev: [feats], both or neither, applied
+ * as (row - mean) / std.  Host arrays: face_ids_host[4] = r_hip, l_hip, sdr_r, sdr_l; foot_ids_host[4] = fid_l[0], fid_l[1], fid_r[0],
+ * fid_r[1] (HML; may be NULL in POSROT); the kinematic chains flattened into chains_host with chain c at
+ * chains_host[chain_starts_host[c] .. chain_starts_host[c + 1]) (HML; num_chains = 0 allowed in POSROT); raw_offsets_host[joints][3]
+ * (HML), the unit bone directions.  feet_thre: the squared-displacement threshold of the contacts.
+ * Outputs: sample_dev [batch][feats][1][frames_out], the samplers' layout: row t < min(len - 1, frames_out) of a clip, exact zeros from
+ * there on (a longer clip is cut); lengths_out_dev [batch] int32 = min(len - 1, frames_out); optional (NULL: not written)
+ * global_positions_dev and local_positions_dev [batch][frames][joints][3] and l_velocity_dev [batch][frames - 1][2], zero past a clip.
+ * Stated deviation: the arcsin argument of the root's angular velocity is clamped into [-1, 1] (the reference returns NaN past 1).
+ * Refused here: frames < 2 or above mst_encode_max_frames, joints outside 2..24, frames_out < 1, a face or foot id out of range, a face id
+ * named twice, a chain that does not start at a joint already placed (joint 0 or an earlier chain's) or that names a joint twice as a
+ * child, POSROT without rotations, HML without foot ids, chains or raw offsets, one of mean / std without the other.
+ * ----------------------------------------------------------------------------------------- */
+int mst_encode_motion(const float* positions_dev, const float* rotations_dev, const int32_t* lengths_dev, const float* mean_dev,
+                      const float* std_dev, int32_t batch, int32_t frames, int32_t joints, int32_t mode, const int32_t* face_ids_host,
+                      const int32_t* foot_ids_host, const int32_t* chains_host, const int32_t* chain_starts_host, int32_t num_chains,
+                      const float* raw_offsets_host, float feet_thre, int32_t frames_out, float* sample_dev, int32_t* lengths_out_dev,
+                      float* global_positions_dev, float* local_positions_dev, float* l_velocity_dev, void* stream);
+/* Longest clip mst_encode_motion takes: the kernel keeps the per-frame forward direction (two fp32 rows) and one root quaternion a frame
+ * in LDS, 24 bytes a frame -- 48 KB at the cap of 2048 -- and recomputes a neighbouring frame's positions from the input, so today the
+ * bound is the same for every joint count and both modes.  -1 for joints outside 2..24 or a mode that is neither 0 nor 1. */
+int mst_encode_max_frames(int32_t joints, int32_t mode);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
