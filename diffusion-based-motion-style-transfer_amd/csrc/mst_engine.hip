@@ -32,6 +32,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_feet.h"
 #include "mst_ik.h"
 #include "mst_encode.h"
+#include "mst_plan.h"
 
 using namespace mst;
 
@@ -226,8 +227,7 @@ struct mst_engine {
     int dbg_layer = -1, dbg_stage = -1;   // stop the trunk after (layer, stage); -1 = run everything
     int fuse_qkv_attn = 1;                // K4 + K5 as one kernel per (clip, head); MST_FUSE_QKV_ATTN=0 keeps them apart
     int fuse_tail = 1;                    // K6 + K7 + K8 as one kernel per 64-token tile (mst_tail.h); MST_FUSE_TAIL=0 keeps them apart
-    int tail_ntb = 0;                     // fused layer tail: 16-token blocks per tile; 0 = per launch (launch_tail), MST_TAIL_NTB=2..4 fixes it
-    int cur_slices = 1;                   // clip slices the launches being enqueued share the chip with (mst_sample_loop; 1 = a lone launch sequence)
+    int tail_ntb = 0;                     // fused layer tail: 16-token blocks per tile; 0 = per launch (plan_trunk), MST_TAIL_NTB=2..4 fixes it
     int trunk_groups = 0;                 // MST_TRUNK=1: the encoder stack of a sampling step as ONE launch of resident workgroup groups (mst_trunk.h)
     unsigned* trunk_cnt = nullptr;        // [max_rows][32]: a clip's arrival counter (one 128-byte line each); every launch finds it at 0 and leaves it at 0
     unsigned* trunk_err = nullptr;        // pinned host word the kernel sets when a bounded spin gives up (mst_trunk_check)
@@ -245,7 +245,7 @@ struct mst_engine {
                                           // re-streaming).  Off by default: wins 16-21 % in gemm_bench, nothing in the pipeline (CFG 39.7 vs
                                           // 39.9, batch 128 77.2 vs 77.1 clips/s; forced at batch 64: 58.7 vs 68.3) -- kept, parity-tested
     int wgrad_stream_on = 1;              // training: wgrads on a second stream beside the dgrad chain (MST_WGRAD_STREAM=0: one stream)
-    int nsplit = 0;                       // clip slices of a sampling loop on separate streams: 0 = chosen per call (loop_slices_for), 1..3 = MST_STREAMS
+    int nsplit = 0;                       // clip slices of a sampling loop on separate streams: 0 = chosen per call (plan_slices), 1..3 = MST_STREAMS
     static constexpr int MAX_SLICES = 8;
     hipStream_t aux_stream[MAX_SLICES - 1] = {nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[MAX_SLICES - 1] = {nullptr};
@@ -288,7 +288,6 @@ struct mst_engine {
     std::vector<int> plan_host;
     hipEvent_t plan_ev = nullptr;         // recorded behind the upload: plan_host is not rewritten before the copy has read it
     StyleSlice plan_sl[MAX_SLICES];
-    const StyleSlice* style_cur = nullptr;   // the slice run_trunk is enqueuing (nullptr: single-style launches)
 };
 
 template <class T>
@@ -793,27 +792,20 @@ template <int KS, int MODE>
 static int launch_rows_gemm(int M, int N, const f16* X, const f16* wpk, const float* bias, void* out, int ldo, hipStream_t st, const LnRows* ln = nullptr,
                             const FfnTrain* ft = nullptr) {
     constexpr int smem = 64 * (KS / 16) * 1024;
-    if constexpr (KS == 16 && (MODE == 0 || MODE == 1 || MODE == 3)) {
-        if (ln) {                                                  // 16-token tiles (mst_small.h)
-            hipLaunchKernelGGL((k_rows_gemm<KS, MODE, 1, 1>), dim3((M + 15) / 16, N / 128), dim3(512), 16 * 1024, st, X, wpk, bias, out, ldo, M, *ln, ft ? *ft : FfnTrain{});
-            HIPCHECK(hipGetLastError());
-            return 0;
-        }
+#define ROWS_LAUNCH(LNF_, NTB_, ln_)                                                                                                       \
+    hipLaunchKernelGGL((k_rows_gemm<KS, MODE, LNF_, NTB_>), dim3((M + 16 * NTB_ - 1) / (16 * NTB_), N / 128), dim3(512), smem * NTB_ / 4, st, X, \
+                       wpk, bias, out, ldo, M, ln_, ft ? *ft : FfnTrain{})
+    if (ln) {                                                      // the LayerNorm in front: 16-token tiles (mst_small.h)
+        if constexpr (KS == 16 && (MODE == 0 || MODE == 1 || MODE == 3)) ROWS_LAUNCH(1, 1, *ln);
+        else return fail("rows GEMM: no fused-LayerNorm instantiation for KS %d MODE %d", KS, MODE);
+    } else switch (rows_ntb(M, g_rows_ntb1_m, g_rows_ntb2_from)) {
+        case 1: ROWS_LAUNCH(0, 1, LnRows{}); break;
+        case 2: ROWS_LAUNCH(0, 2, LnRows{}); break;
+        default:
+            CHECK(ensure_dyn_lds((const void*)k_rows_gemm<KS, MODE>, smem));
+            ROWS_LAUNCH(0, 4, LnRows{});
     }
-    {
-        if (M <= g_rows_ntb1_m) {                                  // a clip or two: 16-token tiles here too (a quarter of the DMA burst in front of the first MFMA)
-            hipLaunchKernelGGL((k_rows_gemm<KS, MODE, 0, 1>), dim3((M + 15) / 16, N / 128), dim3(512), smem / 4, st, X, wpk, bias, out, ldo, M, LnRows{}, ft ? *ft : FfnTrain{});
-            HIPCHECK(hipGetLastError());
-            return 0;
-        }
-        if (M > g_rows_ntb2_from) {
-            hipLaunchKernelGGL((k_rows_gemm<KS, MODE, 0, 2>), dim3((M + 31) / 32, N / 128), dim3(512), smem / 2, st, X, wpk, bias, out, ldo, M, LnRows{}, ft ? *ft : FfnTrain{});
-            HIPCHECK(hipGetLastError());
-            return 0;
-        }
-    }
-    CHECK(ensure_dyn_lds((const void*)k_rows_gemm<KS, MODE>, smem));
-    hipLaunchKernelGGL((k_rows_gemm<KS, MODE>), dim3((M + 63) / 64, N / 128), dim3(512), smem, st, X, wpk, bias, out, ldo, M, LnRows{}, ft ? *ft : FfnTrain{});
+#undef ROWS_LAUNCH
     HIPCHECK(hipGetLastError());
     return 0;
 }
@@ -838,17 +830,19 @@ static int launch_qkv_attn_n(const f16* hx, const f16* w_in, const float* b_in, 
     return 0;
 }
 
-static int launch_qkv_attn(const f16* hx, const f16* w_in, const float* b_in, f16* out, int S, int rows, hipStream_t st) {
-    switch ((S + 31) / 32) {
-        case 1: return launch_qkv_attn_n<1>(hx, w_in, b_in, out, S, rows, st);
-        case 2: return launch_qkv_attn_n<2>(hx, w_in, b_in, out, S, rows, st);
-        case 3: return launch_qkv_attn_n<3>(hx, w_in, b_in, out, S, rows, st);
-        case 4: return launch_qkv_attn_n<4>(hx, w_in, b_in, out, S, rows, st);
-        case 5: return launch_qkv_attn_n<5>(hx, w_in, b_in, out, S, rows, st);
-        case 6: return launch_qkv_attn_n<6>(hx, w_in, b_in, out, S, rows, st);
-        case 7: return launch_qkv_attn_n<7>(hx, w_in, b_in, out, S, rows, st);
-    }
+#define NKT_SWITCH(fn, S, ...)                                    \
+    switch (((S) + 31) / 32) {                                    \
+        case 1: return fn<1>(__VA_ARGS__);                        \
+        case 2: return fn<2>(__VA_ARGS__);                        \
+        case 3: return fn<3>(__VA_ARGS__);                        \
+        case 4: return fn<4>(__VA_ARGS__);                        \
+        case 5: return fn<5>(__VA_ARGS__);                        \
+        case 6: return fn<6>(__VA_ARGS__);                        \
+        case 7: return fn<7>(__VA_ARGS__);                        \
+    }                                                             \
     return fail("attention: S=%d unsupported", S);
+static int launch_qkv_attn(const f16* hx, const f16* w_in, const float* b_in, f16* out, int S, int rows, hipStream_t st) {
+    NKT_SWITCH(launch_qkv_attn_n, S, hx, w_in, b_in, out, S, rows, st)
 }
 
 template <int NT16>
@@ -860,33 +854,24 @@ static int launch_qkv_attn2_n(const f16* hx, const f16* wq, const float* b_in, f
     HIPCHECK(hipGetLastError());
     return 0;
 }
-// The role-swapped kernel holds K, V and Q images of 16 ceil(S / 16) rows in LDS: up to S = 208 (the model's 196 frames + 1).
-static bool qkv_attn2_fits(int S) { return S <= 208; }
-static int launch_qkv_attn2(const f16* hx, const f16* wq, const float* b_in, f16* out, int S, int rows, hipStream_t st) {
-    const int n16 = (S + 15) / 16;
-    switch (n16 == 13 ? 13 : (n16 + 1) / 2 * 2) {
-        case 2: return launch_qkv_attn2_n<2>(hx, wq, b_in, out, S, rows, st);
-        case 4: return launch_qkv_attn2_n<4>(hx, wq, b_in, out, S, rows, st);
-        case 6: return launch_qkv_attn2_n<6>(hx, wq, b_in, out, S, rows, st);
-        case 8: return launch_qkv_attn2_n<8>(hx, wq, b_in, out, S, rows, st);
-        case 10: return launch_qkv_attn2_n<10>(hx, wq, b_in, out, S, rows, st);
-        case 12: return launch_qkv_attn2_n<12>(hx, wq, b_in, out, S, rows, st);
-        case 13: return launch_qkv_attn2_n<13>(hx, wq, b_in, out, S, rows, st);
-    }
+// nt16: TrunkPlan::nt16 (mst_plan.h), shared with the style-aware kernel
+#define NT16_SWITCH(fn, nt16, S, ...)                             \
+    switch (nt16) {                                               \
+        case 2: return fn<2>(__VA_ARGS__);                        \
+        case 4: return fn<4>(__VA_ARGS__);                        \
+        case 6: return fn<6>(__VA_ARGS__);                        \
+        case 8: return fn<8>(__VA_ARGS__);                        \
+        case 10: return fn<10>(__VA_ARGS__);                      \
+        case 12: return fn<12>(__VA_ARGS__);                      \
+        case 13: return fn<13>(__VA_ARGS__);                      \
+    }                                                             \
     return fail("attention: S=%d unsupported", S);
+static int launch_qkv_attn2(const f16* hx, const f16* wq, const float* b_in, f16* out, int S, int rows, int nt16, hipStream_t st) {
+    NT16_SWITCH(launch_qkv_attn2_n, nt16, S, hx, wq, b_in, out, S, rows, st)
 }
 
 static int launch_attn(const f16* qkv, f16* out, int S, int rows, hipStream_t st, int qsplit = 0, f16* out_lo = nullptr) {
-    switch ((S + 31) / 32) {
-        case 1: return launch_attn_n<1>(qkv, out, S, rows, st, qsplit, out_lo);
-        case 2: return launch_attn_n<2>(qkv, out, S, rows, st, qsplit, out_lo);
-        case 3: return launch_attn_n<3>(qkv, out, S, rows, st, qsplit, out_lo);
-        case 4: return launch_attn_n<4>(qkv, out, S, rows, st, qsplit, out_lo);
-        case 5: return launch_attn_n<5>(qkv, out, S, rows, st, qsplit, out_lo);
-        case 6: return launch_attn_n<6>(qkv, out, S, rows, st, qsplit, out_lo);
-        case 7: return launch_attn_n<7>(qkv, out, S, rows, st, qsplit, out_lo);
-    }
-    return fail("attention: S=%d unsupported", S);
+    NKT_SWITCH(launch_attn_n, S, qkv, out, S, rows, st, qsplit, out_lo)
 }
 
 static int rowwise_linear(const float* in, int ldin, const long long* gather, const float* rowscale, int rows_zero_from,
@@ -1025,20 +1010,9 @@ static int ensure_packed(mst_engine* e, hipStream_t st, bool layers = true) {
     return 0;
 }
 
-// K6 + K7 + K8 of one layer as one launch (mst_tail.h): one workgroup per 64-token tile
-static int launch_tail(const mst_engine* e, const LayerW& w, const WS& ws, int M, hipStream_t st) {
+// K6 + K7 + K8 of one layer as one launch (mst_tail.h): one workgroup per tile of 16 ntb tokens (TrunkPlan::tail_ntb)
+static int launch_tail(const mst_engine* e, const LayerW& w, const WS& ws, int M, int ntb, hipStream_t st) {
     static_assert(TailCfg::SMEM <= 163840, "fused layer tail exceeds the 160 KiB LDS");
-    // Tile height (16 NTB tokens; mst_tail.h).  A launch that has the chip to itself and does not fill it runs on more, lower tiles; the
-    // clip slices of a sampling loop share the chip (3 x 68 tiles of 64 tokens at the headline batch) and keep the 64-token tile: 48-token
-    // tiles measured 99.4 against 105.3 clips/s there, 32-token tiles 88.3 (tools/experiments/r4_ntb_ab.sh).
-    int ntb = e->tail_ntb;
-    if (ntb == 0) {
-        ntb = 4;
-        if (e->cur_slices == 1) {
-            if ((M + 31) / 32 <= 256) ntb = 2;
-            else if ((M + 47) / 48 <= 256) ntb = 3;
-        }
-    }
     const int grid = (M + 16 * ntb - 1) / (16 * ntb);
 #define TAIL_LAUNCH(N_)                                                                                                          \
     do {                                                                                                                         \
@@ -1054,12 +1028,7 @@ static int launch_tail(const mst_engine* e, const LayerW& w, const WS& ws, int M
     return 0;
 }
 
-// The whole stack of a sampling step as one launch of resident groups (mst_trunk.h): frame counts whose token count is 13 blocks of 16
-// (193 .. 208 tokens: the model's 196 frames), the default fused kernels, no debug stop, no instrumented step, at most 8 layers.
-static bool trunk_groups_fit(const mst_engine* e, int S) {
-    return e->trunk_groups && (S + 15) / 16 == 13 && e->fuse_qkv_attn == 1 && e->fuse_tail && e->tail_ntb == 0 && e->dbg_stage < 0 && !e->precise &&
-           e->cfg.num_layers <= 8;
-}
+// The whole stack of a sampling step as one launch of resident groups (mst_trunk.h; PATH_RESIDENT in mst_plan.h)
 static int launch_trunk_groups(mst_engine* e, const WS& ws, int S, int rows, hipStream_t st) {
     using TT = TrunkTile<13>;
     if (e->trunk_err[0]) return fail("resident-group trunk: a hand-off wait gave up in an earlier launch (results of that loop are invalid)");
@@ -1278,7 +1247,7 @@ static int style_check(const mst_engine* e, int batch, int frames) {
     return 0;
 }
 
-// This call's tables: for each slice (enqueue_step's split of the batch; cond + uncond twins of a clip share its slot) the slot of every
+// This call's tables: for each slice (slice_of's split of the batch; cond + uncond twins of a clip share its slot) the slot of every
 // transformer row, the clip order of the attention launch and the segments of every tile height -- built once and uploaded in ONE copy.
 static int style_plan(mst_engine* e, int batch, int cfg, int frames, int nsl, hipStream_t st) {
     const int S = frames + 1;
@@ -1287,11 +1256,10 @@ static int style_plan(mst_engine* e, int batch, int cfg, int frames, int nsl, hi
     std::vector<int>& h = e->plan_host;
     h.clear();
     auto align4 = [&]() { while (h.size() & 3) h.push_back(0); };
-    const int per = (batch + nsl - 1) / nsl;
     for (int sl = 0; sl < nsl; sl++) {
         StyleSlice& ps = e->plan_sl[sl];
         ps = StyleSlice{};
-        const int c0 = sl * per, nb = (c0 + per <= batch) ? per : batch - c0;
+        const int c0 = slice_of(batch, nsl, sl).first, nb = slice_of(batch, nsl, sl).clips;
         if (nb <= 0) continue;
         const int rows = cfg ? 2 * nb : nb;
         std::vector<int> slot(rows);
@@ -1340,11 +1308,12 @@ static int launch_rows_seg(mst_engine* e, const StyleSlice& ps, int l, const f16
     HIPCHECK(hipGetLastError());
     return 0;
 }
-// launch_rows_gemm's tile-height rule, per segment table
+// launch_rows_gemm's tile heights, per segment table
 template <int KS, int MODE>
 static int launch_rows_seg_m(mst_engine* e, const StyleSlice& ps, int l, int M, const f16* X, void* out, int ldo, int N, hipStream_t st) {
-    if (M <= g_rows_ntb1_m) return launch_rows_seg<KS, MODE, 0, 1>(e, ps, l, X, out, ldo, N, LnRows{}, st);
-    if (M > g_rows_ntb2_from) return launch_rows_seg<KS, MODE, 0, 2>(e, ps, l, X, out, ldo, N, LnRows{}, st);
+    const int ntb = rows_ntb(M, g_rows_ntb1_m, g_rows_ntb2_from);
+    if (ntb == 1) return launch_rows_seg<KS, MODE, 0, 1>(e, ps, l, X, out, ldo, N, LnRows{}, st);
+    if (ntb == 2) return launch_rows_seg<KS, MODE, 0, 2>(e, ps, l, X, out, ldo, N, LnRows{}, st);
     return launch_rows_seg<KS, MODE, 0, 4>(e, ps, l, X, out, ldo, N, LnRows{}, st);
 }
 static int launch_ln_style(mst_engine* e, const StyleSlice& ps, int l, int which, const float* acc, f16* hi, f16* lo, int M, int S, hipStream_t st,
@@ -1364,28 +1333,10 @@ static int launch_qkv_attn2_style_n(mst_engine* e, const StyleSlice& ps, int l, 
     HIPCHECK(hipGetLastError());
     return 0;
 }
-static int launch_qkv_attn2_style(mst_engine* e, const StyleSlice& ps, int l, const WS& ws, int S, int rows, hipStream_t st) {
-    const int n16 = (S + 15) / 16;
-    switch (n16 == 13 ? 13 : (n16 + 1) / 2 * 2) {
-        case 2: return launch_qkv_attn2_style_n<2>(e, ps, l, ws, S, rows, st);
-        case 4: return launch_qkv_attn2_style_n<4>(e, ps, l, ws, S, rows, st);
-        case 6: return launch_qkv_attn2_style_n<6>(e, ps, l, ws, S, rows, st);
-        case 8: return launch_qkv_attn2_style_n<8>(e, ps, l, ws, S, rows, st);
-        case 10: return launch_qkv_attn2_style_n<10>(e, ps, l, ws, S, rows, st);
-        case 12: return launch_qkv_attn2_style_n<12>(e, ps, l, ws, S, rows, st);
-        case 13: return launch_qkv_attn2_style_n<13>(e, ps, l, ws, S, rows, st);
-    }
-    return fail("attention: S=%d unsupported", S);
+static int launch_qkv_attn2_style(mst_engine* e, const StyleSlice& ps, int l, const WS& ws, int S, int rows, int nt16, hipStream_t st) {
+    NT16_SWITCH(launch_qkv_attn2_style_n, nt16, S, e, ps, l, ws, S, rows, st)
 }
-static int launch_tail_style(mst_engine* e, const StyleSlice& ps, int l, const WS& ws, int M, hipStream_t st) {
-    int ntb = e->tail_ntb;                                   // launch_tail's tile-height rule
-    if (ntb == 0) {
-        ntb = 4;
-        if (e->cur_slices == 1) {
-            if ((M + 31) / 32 <= 256) ntb = 2;
-            else if ((M + 47) / 48 <= 256) ntb = 3;
-        }
-    }
+static int launch_tail_style(mst_engine* e, const StyleSlice& ps, int l, const WS& ws, int ntb, hipStream_t st) {
     const int hi = style_h_index(16 * ntb), nl = e->cfg.num_layers;
     const StyleSeg* segs = reinterpret_cast<const StyleSeg*>(e->plan_dev + ps.off_seg[hi]);
 #define TAIL_SEG(N_)                                                                                                               \
@@ -1404,11 +1355,10 @@ static int launch_tail_style(mst_engine* e, const StyleSlice& ps, int l, const W
 
 // run_trunk for a batch of several styles: the default fused path (style_check has refused everything else), each launch reading the
 // slice's tables.  Same launch sequence and tile heights as the single-style path.
-static int run_trunk_style(mst_engine* e, const WS& ws, int rows, int T, hipStream_t st, const StyleSlice& ps) {
+static int run_trunk_style(mst_engine* e, const WS& ws, int rows, int T, hipStream_t st, const StyleSlice& ps, const TrunkPlan& tp) {
     const int S = T + 1, M = rows * S, NL = e->cfg.num_layers;
     if (ps.rows != rows) return fail("several styles: slice of %d rows, plan of %d", rows, ps.rows);
-    const bool small = e->small_m > 0 && M <= e->small_m;
-    const bool lnf = small && e->small_ln && M <= e->small_ln_m;
+    const bool small = tp.path != PATH_LARGE, lnf = tp.lnf;
     for (int l = 0; small && l < NL; l++) {
         {
             ProfScope pq(e, FAM_QKV, st);
@@ -1443,11 +1393,11 @@ static int run_trunk_style(mst_engine* e, const WS& ws, int rows, int T, hipStre
     for (int l = 0; !small && l < NL; l++) {
         {
             ProfScope pq(e, FAM_QKV_ATTN, st);
-            CHECK(launch_qkv_attn2_style(e, ps, l, ws, S, rows, st));
+            CHECK(launch_qkv_attn2_style(e, ps, l, ws, S, rows, tp.nt16, st));
         }
         {
             ProfScope pt(e, FAM_TAIL, st);
-            CHECK(launch_tail_style(e, ps, l, ws, M, st));
+            CHECK(launch_tail_style(e, ps, l, ws, tp.tail_ntb, st));
         }
     }
     return 0;
@@ -1512,28 +1462,21 @@ static int assemble_stream(mst_engine* e, const WS& ws, const float* x, int clip
     return 0;
 }
 
-// K3 .. K8: token stream through the encoder stack.  rows = clips through the transformer.
+// K3 .. K8: token stream through the encoder stack.  rows = clips through the transformer; tp = plan_trunk of this launch sequence
+// (mst_plan.h); style = the slice's tables when the batch holds several styles (nullptr: single-style launches).
 static int run_trunk(mst_engine* e, const WS& ws, const float* x, int clips_x, int rows, int T, int temb_uniform_row, int temb_mod,
-                     hipStream_t st, int tp_uncond = 0, LoopRef lr = LoopRef()) {
+                     hipStream_t st, const TrunkPlan& tp, const StyleSlice* style, int tp_uncond = 0, LoopRef lr = LoopRef()) {
     const int S = T + 1, M = rows * S;
     CHECK(assemble_stream(e, ws, x, clips_x, rows, T, temb_uniform_row, temb_mod, st, tp_uncond, lr));
     if (e->dbg_stage == 0) return 0;
-    if (e->style_cur) return run_trunk_style(e, ws, rows, T, st, *e->style_cur);
+    if (style) return run_trunk_style(e, ws, rows, T, st, *style, tp);
 #define DBG_STOP(stage) if (e->dbg_layer == l && e->dbg_stage == stage) return 0;
-    const bool small = e->precise || (e->small_m > 0 && M <= e->small_m);
-    // Clips of at most 16 frames: so few values are averaged per output that the f16 rounding of the ACTIVATION operands shows at the
-    // 1e-3 bar (oracle rounding model, classifier-free guidance: 1.07e-3 mean over seeds at 1 frame, 9.1e-4 at 5 frames, 7.6e-4 at
-    // 196).  Those launches -- a handful of tiles, nowhere near a throughput regime -- multiply every activation as hi + lo
-    // (RowsDirect::Xlo; the lo halves of att and hid borrow the idle hid / qkv buffers): 6.5e-4 mean in the same model.
-    const bool precise = e->precise || (small && T <= 16);
-    f16* const att_lo = precise ? ws.hid : nullptr;
-    f16* const hid_lo = precise ? ws.qkv : nullptr;
-    const f16* const hl_in = precise ? ws.hl : nullptr;
-    // round 4: without split operands the four GEMMs run as resident-tile / streamed-weight kernels (mst_small.h; MST_SMALL_FAST=0: the ring)
-    const bool fast = small && !precise && e->small_fast;
-    // ... and the LayerNorms inside the GEMM behind them (LnRows): LN1 in FFN1, which leaves the stream in (hx2, hl2); LN2 in the next
-    // layer's QKV GEMM, which brings it back to (hx, hl); the last LN2 as the rows kernel (MST_SMALL_LN=0: every LayerNorm a launch)
-    const bool lnf = fast && e->small_ln && e->dbg_stage < 0 && M <= e->small_ln_m;
+    const bool small = tp.path <= PATH_SMALL_ROWS_LN, fast = small && tp.path != PATH_SMALL_RING, lnf = tp.lnf;
+    // split operands (RowsDirect::Xlo): the lo halves of att and hid borrow the idle hid / qkv buffers
+    f16 *const att_lo = tp.precise ? ws.hid : nullptr, *const hid_lo = tp.precise ? ws.qkv : nullptr;
+    const f16* const hl_in = tp.precise ? ws.hl : nullptr;
+    // lnf (LnRows): LN1 in FFN1, which leaves the stream in (hx2, hl2); LN2 in the next layer's QKV GEMM, which brings it back to
+    // (hx, hl); the last LN2 as the rows kernel
     const int NL = e->cfg.num_layers;
     for (int l = 0; small && l < NL; l++) {
         const LayerW& w = e->L[l];
@@ -1591,17 +1534,12 @@ static int run_trunk(mst_engine* e, const WS& ws, const float* x, int clips_x, i
         }
         DBG_STOP(5)
     }
-    if (!small && !e->prof_now && trunk_groups_fit(e, S)) {
-        CHECK(launch_trunk_groups(e, ws, S, rows, st));
-        return 0;
-    }
+    if (tp.path == PATH_RESIDENT) return launch_trunk_groups(e, ws, S, rows, st);
     for (int l = 0; !small && l < e->cfg.num_layers; l++) {
         const LayerW& w = e->L[l];
-        if (e->fuse_qkv_attn && !(e->dbg_layer == l && e->dbg_stage == 1)) {
+        if (tp.qkv_attn != QA_UNFUSED && !(e->dbg_layer == l && e->dbg_stage == 1)) {
             ProfScope ps(e, FAM_QKV_ATTN, st);
-            // 1 (default): weights streamed to registers, tokens through the ring; 2: round 2's kernel (both operands through the ring),
-            // which also takes S = 209..224
-            if (e->fuse_qkv_attn == 1 && qkv_attn2_fits(S)) CHECK(launch_qkv_attn2(ws.hx, w.wqkv, w.b_in, ws.att, S, rows, st));
+            if (tp.qkv_attn == QA_STREAMED) CHECK(launch_qkv_attn2(ws.hx, w.wqkv, w.b_in, ws.att, S, rows, tp.nt16, st));
             else CHECK(launch_qkv_attn(ws.hx, w.w_in, w.b_in, ws.att, S, rows, st));
         } else {
             {
@@ -1616,16 +1554,16 @@ static int run_trunk(mst_engine* e, const WS& ws, const float* x, int clips_x, i
             }
         }
         DBG_STOP(2)
-        if (e->fuse_tail && !(e->dbg_layer == l && (e->dbg_stage == 3 || e->dbg_stage == 4))) {
+        if (tp.fuse_tail && !(e->dbg_layer == l && (e->dbg_stage == 3 || e->dbg_stage == 4))) {
             ProfScope ps(e, FAM_TAIL, st);
-            CHECK(launch_tail(e, w, ws, M, st));
+            CHECK(launch_tail(e, w, ws, M, tp.tail_ntb, st));
             DBG_STOP(5)
             continue;
         }
         {
             ProfScope ps(e, FAM_OUTPROJ_LN, st);
             DEpiResidLN epi{w.b_out, w.g1, w.be1, ws.hx, ws.hl, M};
-            if (M >= e->ln128_min_m)
+            if (tp.ln128)
                 CHECK((launch_gemm_dma<128, 512, 2, 4, 2, 1, 64>(dim3((M + 127) / 128, 1), RowsDirect{ws.att, MST_D}, w.w_out, MST_D, MST_D, epi, st)));
             else
                 CHECK((launch_gemm_dma<64, 512, 2, 2, LN_NS, 1, LN_BK>(dim3((M + 63) / 64, 1), RowsDirect{ws.att, MST_D}, w.w_out, MST_D, MST_D, epi, st)));
@@ -1645,7 +1583,7 @@ static int run_trunk(mst_engine* e, const WS& ws, const float* x, int clips_x, i
         {
             ProfScope ps(e, FAM_FFN2_LN, st);
             DEpiResidLN epi{w.b2, w.g2, w.be2, ws.hx, ws.hl, M};
-            if (M >= e->ln128_min_m)
+            if (tp.ln128)
                 CHECK((launch_gemm_dma<128, 512, 2, 4, 2, 1, 64>(dim3((M + 127) / 128, 1), RowsDirect{ws.hid, MST_FF}, w.w2, MST_FF, MST_FF, epi, st)));
             else
                 CHECK((launch_gemm_dma<64, 512, 2, 2, LN_NS, 1, LN_BK>(dim3((M + 63) / 64, 1), RowsDirect{ws.hid, MST_FF}, w.w2, MST_FF, MST_FF, epi, st)));
@@ -1743,6 +1681,12 @@ static int launch_out_nt(mst_engine* e, const WS& ws, int cfg, int batch, int T,
     return launch_out_nx<MODE, 512, 2, 2>(e, ws, cfg, batch, T, out, sa, st, wo, bo, tok_off, frames_next, hi_lo);
 }
 
+// the switches mst_plan.h decides by, as they stand now (mst_set_precise, mst_set_trunk_groups and mst_debug_stop_after change them between calls)
+static PlanKnobs plan_knobs(const mst_engine* e) {
+    return PlanKnobs{e->small_m, e->small_ln, e->small_ln_m, e->small_fast, e->precise, e->fuse_qkv_attn, e->fuse_tail, e->tail_ntb, e->ln128_min_m,
+                     e->trunk_groups, e->cfg.num_layers, e->nsplit, e->dbg_stage >= 0};
+}
+
 static int check_ready(mst_engine* e, int batch, int frames, int cfg) {
     if (!e) return fail("null engine");
     CHECK(mst_weights_complete(e));
@@ -1764,112 +1708,86 @@ extern "C" int mst_forward(mst_engine* e, const float* x, const int64_t* t, cons
     hipStream_t st = (hipStream_t)stream;
     ON_DEVICE(e->cfg.device);
     e->prof_now = e->prof_on;
-    e->cur_slices = 1;
     CHECK(ensure_packed(e, st));
     CHECK(timestep_rows(e, (const long long*)t, batch, st));
     const int rows = cfg ? 2 * batch : batch;
     const WS ws = ws_slice(e, 0, frames);
-    e->style_cur = nullptr;
     if (styles_on(e)) {
         CHECK(style_check(e, batch, frames));
         CHECK(style_plan(e, batch, cfg, frames, 1, st));
-        e->style_cur = &e->plan_sl[0];
     }
-    const int rc = run_trunk(e, ws, x, batch, rows, frames, -1, batch, st, batch);
-    e->style_cur = nullptr;
-    CHECK(rc);
+    CHECK(run_trunk(e, ws, x, batch, rows, frames, -1, batch, st, plan_trunk(plan_knobs(e), rows, frames, 1, e->prof_now),
+                    styles_on(e) ? &e->plan_sl[0] : nullptr, batch));
     StepArgs sa{};
     sa.scale = scale;
     return trunk_settle(e, st, launch_out_nt<0>(e, ws, cfg, batch, frames, out, sa, st, nullptr, nullptr, 1, false, true));
 }
 
-// How many independent clip slices a loop over `batch` clips of `frames` frames runs as.  Measured, same box, interleaved
-// (tools/experiments/streams_ab.sh, tools/experiments/streams_ab_configs.sh), round-2 kernels at 196 frames: a batch whose tiles are all resident at
-// once on the large-tile path wanted ONE slice (batch 64: 82.0 / 81.6 / 80.6 clips/s at 1 / 2 / 3 slices; batch 32: 43.8 vs 39.7
-// at 3 -- slices would drop to the small-tile kernels); more tiles than CUs want one slice per round of tiles (batch 128 = 394
-// tiles: 78.5 / 91.2 / 88.0 at 1 / 2 / 3; CFG at 64 clips: 39.8 / 45.5 / 44.6); the small-tile path (batch 16: 22.1 vs 28.8) up to three.
-static int loop_slices_for(const mst_engine* e, int batch, int cfg, int frames) {
-    if (!e || e->dbg_stage >= 0) return 1;
-    const int rows = (cfg ? 2 : 1) * batch;
-    int n = e->nsplit;
-    if (n == 0 && trunk_groups_fit(e, frames + 1) && !(e->small_m > 0 && (long long)rows * (frames + 1) <= e->small_m)) return 1;   // every clip is a chain of its own inside ONE launch
-    if (n == 0) {
-        const long long M = (long long)rows * (frames + 1);
-        const bool small = e->precise || (e->small_m > 0 && M <= e->small_m);
-        const long long tiles = (M + 63) / 64, waves = (tiles + 255) / 256;      // rounds of 64-token tiles over the 256 CUs
-        n = small ? 3 : (int)(waves < 3 ? waves : 3);
-        // Round 3: a batch that fills most of the chip in ONE round (the headline: 64 clips = 197 tiles) runs every workgroup through the
-        // same phase at the same time; three slices of it (each still on the large-tile path) decorrelate them.  Same-box, interleaved,
-        // 1 vs 3 slices at 64 clips: 96.9 vs 98.9 clips/s on a slow box (three rounds), 103.2 vs 104.1 on a fast one; at 48 clips
-        // (148 tiles) two slices are a wash (84.0 vs 83.7) and three fall to the small-tile kernels.
-        if (!small && waves == 1 && tiles >= 192) n = 3;
-    }
-    while (n > 1 && rows / n < 8) n--;                       // at least 8 rows through the transformer per slice
-    return n;
-}
 extern "C" int mst_loop_slices(const mst_engine* e, int32_t batch, int32_t cfg, int32_t frames) {
-    return loop_slices_for(e, batch, cfg, frames > 0 ? frames : (e ? e->cfg.max_frames : 0));
+    return e ? plan_slices(plan_knobs(e), batch, cfg, frames > 0 ? frames : e->cfg.max_frames) : 1;
 }
 
-// One denoise step of every slice, enqueued (or captured): slice sl on streams[sl]; step = *ld.jbase + joff.
 struct LoopPlan {
     const mst_schedule* s; const mst_loop_args* a; int nsl; size_t per_clip, clip_elems;
     hipStream_t streams[mst_engine::MAX_SLICES];
     const mst_guide_args* gd = nullptr;      // mst_sample_loop_guided: the step kernels are the guided MODEs
 };
+// One slice of a loop's launch sequence: its clips, its rows of the workspace, its stream, its style tables and its trunk plan;
+// for_each_slice calls body(SliceCtx) for every non-empty slice of the batch in nsl slices (slice sl on p.streams[sl]).
+struct SliceCtx { int c0, nb; size_t eo; WS ws; hipStream_t ss; const StyleSlice* style; TrunkPlan tp; };
+template <class Body>
+static int for_each_slice(mst_engine* e, const LoopPlan& p, int nsl, const Body& body) {
+    const mst_loop_args* a = p.a;
+    const PlanKnobs k = plan_knobs(e);
+    for (int sl = 0; sl < nsl; sl++) {
+        const SliceRange r = slice_of(a->batch, nsl, sl);
+        if (r.clips <= 0) continue;
+        // workspace rows of the slice: its clips (cond + uncond twins under CFG); text projections are indexed in the full-batch
+        // layout [cond 0..B | uncond 0..B].  (Several styles: the tables are planned for p.nsl slices; instrumented steps are refused.)
+        WS ws = ws_slice(e, a->cfg ? 2 * r.first : r.first, a->frames);
+        ws.textproj = e->textproj + (size_t)r.first * MST_D;
+        CHECK(body(SliceCtx{r.first, r.clips, (size_t)r.first * p.per_clip, ws, p.streams[sl], styles_on(e) ? &e->plan_sl[sl] : nullptr,
+                            plan_trunk(k, a->cfg ? 2 * r.clips : r.clips, a->frames, nsl, e->prof_now)}));
+    }
+    return 0;
+}
+// MODE of a loop step's output projection (DEpiEmbedOut<MODE>; 0 = the model output alone)
+static int step_mode(int sampler, bool guided) {
+    if (guided) return sampler == MST_SAMPLER_DDPM ? 5 : 6;
+    return sampler == MST_SAMPLER_DDPM ? 1 : sampler == MST_SAMPLER_DDIM_REVERSE ? 3 : sampler == MST_SAMPLER_PLMS ? 4 : 2;
+}
+// One denoise step of every slice, enqueued (or captured); step = *ld.jbase + joff.
 // frames_ready / frames_next: the step's frame rows (ws.xt) were written by the previous step's epilogue / this step's epilogue
 // writes them for the next one (mst_sample_loop decides; see DEpiEmbedOut::xt_next)
 // stream_ready / embed_next: the previous step's output projection embedded this step / this step's embeds the next (k_embed_out<.., KSN>)
 static int enqueue_step(mst_engine* e, const LoopPlan& p, int joff, int nsj, bool frames_ready = false, bool frames_next = false,
                         bool stream_ready = false, bool embed_next = false) {
     const mst_loop_args* a = p.a;
-    e->cur_slices = nsj;
-    for (int sl = 0; sl < nsj; sl++) {
-        const int per = (a->batch + nsj - 1) / nsj;          // clips per slice (last one may be short)
-        const int c0 = sl * per;
-        const int nb = (c0 + per <= a->batch) ? per : a->batch - c0;
-        if (nb <= 0) continue;
-        const size_t eo = (size_t)c0 * p.per_clip;
-        // workspace rows of the slice: its clips (cond + uncond twins under CFG); text projections are indexed
-        // in the full-batch layout [cond 0..B | uncond 0..B]
-        WS ws = ws_slice(e, a->cfg ? 2 * c0 : c0, a->frames);
-        ws.textproj = e->textproj + (size_t)c0 * MST_D;
-        hipStream_t ss = p.streams[sl];
+    return for_each_slice(e, p, nsj, [&](const SliceCtx& c) -> int {
+        const auto& [c0, nb, eo, ws, ss, style, tp] = c;
         LoopRef lr{e->ld_dev, joff, eo, frames_ready, stream_ready};
-        e->style_cur = styles_on(e) ? &e->plan_sl[sl] : nullptr;     // (mst_sample_loop planned nsj = p.nsl slices: instrumented steps are refused)
-        const int rc = run_trunk(e, ws, nullptr, nb, a->cfg ? 2 * nb : nb, a->frames, 0, 0, ss, a->batch, lr);
-        e->style_cur = nullptr;
-        CHECK(rc);
+        CHECK(run_trunk(e, ws, nullptr, nb, a->cfg ? 2 * nb : nb, a->frames, 0, 0, ss, tp, style, a->batch, lr));
         const DEpiEmbedIn next_epi = embed_in_epi(e, ws, nb, nb, a->frames, 0, 0, a->batch, e->ld_dev, joff + 1);
         const DEpiEmbedIn* next = embed_next ? &next_epi : nullptr;
         StepArgs sa{};
-        sa.tab = p.s->tab;
-        sa.nsteps = p.s->n;
+        sa.tab = p.s->tab; sa.nsteps = p.s->n;
         // presence flags: the kernel resolves the pointers from *ld (step_resolve)
         const float* const yes = reinterpret_cast<const float*>(1);
-        sa.mask = a->inpainting_mask_dev ? yes : nullptr;
-        sa.motion = a->inpainted_motion_dev ? yes : nullptr;
+        sa.mask = a->inpainting_mask_dev ? yes : nullptr; sa.motion = a->inpainted_motion_dev ? yes : nullptr;
         const bool draws = a->sampler != MST_SAMPLER_DDIM_REVERSE && a->sampler != MST_SAMPLER_PLMS;      // the reverse and PLMS steps have no noise term: noise_mode, seed, noise_dev, mask_noise are not read
         sa.noise = draws && a->noise_mode == MST_NOISE_BUFFER ? yes : nullptr;
-        sa.scale = a->scale_dev ? yes : nullptr;
-        sa.xstart = a->xstart_dump_dev ? reinterpret_cast<float*>(1) : nullptr;
-        sa.clip0 = (unsigned)c0;
-        sa.mask_noise = draws ? a->mask_noise : 0;
-        sa.clip = a->clip_denoised;
+        sa.scale = a->scale_dev ? yes : nullptr; sa.xstart = a->xstart_dump_dev ? reinterpret_cast<float*>(1) : nullptr;
+        sa.clip0 = (unsigned)c0; sa.mask_noise = draws ? a->mask_noise : 0; sa.clip = a->clip_denoised;
         sa.philox = draws && a->noise_mode == MST_NOISE_PHILOX;
-        sa.ld = e->ld_dev;
-        sa.joff = joff;
-        sa.eo = eo;
-        sa.step_stride = p.clip_elems;
+        sa.ld = e->ld_dev; sa.joff = joff; sa.eo = eo; sa.step_stride = p.clip_elems;
         sa.rowflag = (a->inpainting_mask_dev && a->inpainted_motion_dev) ? e->rowflag + (size_t)c0 * e->cfg.feats : nullptr;
-        if (p.gd && a->sampler == MST_SAMPLER_DDPM) CHECK(launch_out_nt<5>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
-        else if (p.gd) CHECK(launch_out_nt<6>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
-        else if (a->sampler == MST_SAMPLER_DDPM) CHECK(launch_out_nt<1>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
-        else if (a->sampler == MST_SAMPLER_DDIM_REVERSE) CHECK(launch_out_nt<3>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
-        else if (a->sampler == MST_SAMPLER_PLMS) CHECK(launch_out_nt<4>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
-        else CHECK(launch_out_nt<2>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next));
-    }
-    return 0;
+        switch (step_mode(a->sampler, p.gd != nullptr)) {
+#define OUT(M_) case M_: return launch_out_nt<M_>(e, ws, a->cfg, nb, a->frames, nullptr, sa, ss, nullptr, nullptr, 1, frames_next, true, next);
+            OUT(1) OUT(2) OUT(3) OUT(4) OUT(5) OUT(6)
+#undef OUT
+        }
+        return fail("mst_sample_loop: no step kernel for sampler %d", a->sampler);
+    });
 }
 // The step that opens a PLMS chain of order > 1 (Pseudo Improved Euler, gaussian_diffusion.py:1134-1141): once per chain, so not fused.
 // Per slice, on its stream: the model at (x, t_start) through the model-output-only projection (MODE 0), k_plms_epilogue's first half
@@ -1878,17 +1796,9 @@ static int enqueue_step(mst_engine* e, const LoopPlan& p, int joff, int nsj, boo
 // Always enqueued from the host; the step behind it starts from x in memory (no chained frame rows, no pre-embedded stream).
 static int enqueue_plms_warmup(mst_engine* e, const LoopPlan& p, const mst_plms_args* pl) {
     const mst_loop_args* a = p.a;
-    e->cur_slices = p.nsl;
     const int gx = (int)((p.per_clip + 255) / 256);
-    for (int sl = 0; sl < p.nsl; sl++) {
-        const int per = (a->batch + p.nsl - 1) / p.nsl;
-        const int c0 = sl * per;
-        const int nb = (c0 + per <= a->batch) ? per : a->batch - c0;
-        if (nb <= 0) continue;
-        const size_t eo = (size_t)c0 * p.per_clip;
-        WS ws = ws_slice(e, a->cfg ? 2 * c0 : c0, a->frames);
-        ws.textproj = e->textproj + (size_t)c0 * MST_D;
-        hipStream_t ss = p.streams[sl];
+    return for_each_slice(e, p, p.nsl, [&](const SliceCtx& c) -> int {
+        const auto& [c0, nb, eo, ws, ss, style, tp] = c;
         float* const out = e->plms_out + eo;
         float* const x = a->x_dev + eo;
         float* const h0 = pl->hist_dev + eo;
@@ -1898,10 +1808,7 @@ static int enqueue_plms_warmup(mst_engine* e, const LoopPlan& p, const mst_plms_
         const float* const motion = blend ? a->inpainted_motion_dev + eo : nullptr;
         for (int half = 0; half < 2; half++) {
             LoopRef lr{e->ld_dev, half, eo, false, false};
-            e->style_cur = styles_on(e) ? &e->plan_sl[sl] : nullptr;
-            const int rc = run_trunk(e, ws, nullptr, nb, a->cfg ? 2 * nb : nb, a->frames, 0, 0, ss, a->batch, lr);
-            e->style_cur = nullptr;
-            CHECK(rc);
+            CHECK(run_trunk(e, ws, nullptr, nb, a->cfg ? 2 * nb : nb, a->frames, 0, 0, ss, tp, style, a->batch, lr));
             StepArgs sa{};
             sa.scale = a->scale_dev ? a->scale_dev + c0 : nullptr;
             CHECK(launch_out_nt<0>(e, ws, a->cfg, nb, a->frames, out, sa, ss, nullptr, nullptr, 1, false, true));
@@ -1914,8 +1821,8 @@ static int enqueue_plms_warmup(mst_engine* e, const LoopPlan& p, const mst_plms_
                                    a->t_start, (long long)p.per_clip, a->clip_denoised, x);
             HIPCHECK(hipGetLastError());
         }
-    }
-    return 0;
+        return 0;
+    });
 }
 static int fork_slices(mst_engine* e, const LoopPlan& p) {
     HIPCHECK(hipEventRecord(e->ev_fork, p.streams[0]));
@@ -1977,7 +1884,7 @@ static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_
     // Clips are independent, so the batch runs as `nsplit` slices on separate streams: one slice's kernels fill
     // the CUs the other leaves idle in its prologues, tails and launch gaps (per-launch time is per-CU bound and
     // flat in the block count at this size).  CFG batches are sliced the same way (cond + uncond twins stay together).
-    LoopPlan p{s, a, loop_slices_for(e, a->batch, a->cfg, a->frames), (size_t)e->cfg.feats * a->frames, (size_t)a->batch * e->cfg.feats * a->frames,
+    LoopPlan p{s, a, plan_slices(plan_knobs(e), a->batch, a->cfg, a->frames), (size_t)e->cfg.feats * a->frames, (size_t)a->batch * e->cfg.feats * a->frames,
                {st, e->aux_stream[0], e->aux_stream[1], e->aux_stream[2], e->aux_stream[3], e->aux_stream[4], e->aux_stream[5], e->aux_stream[6]}};
     p.gd = gd;
     if (styles_on(e)) CHECK(style_plan(e, a->batch, a->cfg, a->frames, p.nsl, st));     // before the fork: every slice stream is behind it
@@ -2004,9 +1911,9 @@ static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_
     const int U = e->graph_steps;
     std::vector<long long> key = {a->batch, a->frames, a->cfg, a->sampler, a->noise_mode, a->mask_noise, a->clip_denoised,
                                   a->inpainting_mask_dev != nullptr, a->inpainted_motion_dev != nullptr, a->xstart_dump_dev != nullptr,
-                                  a->scale_dev != nullptr, p.nsl, U, (long long)(size_t)s->tab, s->n, e->small_m, e->fuse_tail,
-                                  e->fuse_qkv_attn, e->ln128_min_m, e->precise, e->tail_ntb, e->embed_fast, e->small_fast, e->small_ln,
-                                  gd != nullptr};      // every switch run_trunk / loop_slices_for / enqueue_step branch on
+                                  a->scale_dev != nullptr, p.nsl, U, (long long)(size_t)s->tab, s->n, e->embed_fast, gd != nullptr};
+    const PlanKnobs knobs = plan_knobs(e);     // ... and every switch the launch plan reads, word by word: a knob added to PlanKnobs is in the key
+    key.insert(key.end(), reinterpret_cast<const int*>(&knobs), reinterpret_cast<const int*>(&knobs) + PLAN_KNOB_WORDS);
     const int j0 = warm ? 1 : 0;                              // the warm-up is the call's step 0
     const bool use_graph = e->graph_on && !e->prof_on && e->dbg_stage < 0 && nrun - j0 >= 2 * U;
     bool forked = false;
@@ -2395,17 +2302,6 @@ static int launch_attn_bwd_n(const f16* qkv, const f16* att, const f16* datt, f1
     HIPCHECK(hipGetLastError());
     return 0;
 }
-#define NKT_SWITCH(fn, S, ...)                                    \
-    switch (((S) + 31) / 32) {                                    \
-        case 1: return fn<1>(__VA_ARGS__);                        \
-        case 2: return fn<2>(__VA_ARGS__);                        \
-        case 3: return fn<3>(__VA_ARGS__);                        \
-        case 4: return fn<4>(__VA_ARGS__);                        \
-        case 5: return fn<5>(__VA_ARGS__);                        \
-        case 6: return fn<6>(__VA_ARGS__);                        \
-        case 7: return fn<7>(__VA_ARGS__);                        \
-    }                                                             \
-    return fail("attention: S=%d unsupported", S);
 static int launch_attn_train(const f16* qkv, f16* out, int S, int rows, Drop d, const unsigned char* keep, int qsplit, float* lse, hipStream_t st) {
     NKT_SWITCH(launch_attn_train_n, S, qkv, out, S, rows, d, keep, qsplit, lse, st)
 }

@@ -23,7 +23,8 @@ import guide_fixture as gf
 import mst_amd  # noqa: F401
 import mst_amd.synthetic as syn
 from conftest import SEED, rel_l2
-from test_gpu_noise import SMALL_M, draw_site, plain_path, slices
+from plan_mirror import SMALL_M, plain_path, slices
+from test_gpu_noise import draw_site
 from test_gpu_reverse import EMB, RSCA, SCA, TOL, VEC, _model, _step_inputs, cu, dev, embeds_next, make, sched, within
 
 pytestmark = pytest.mark.gpu

@@ -10,7 +10,7 @@
                                                             more than 384 features, which no test of the suite runs)
        finish-scalar  mst_gemm_dma.h DEpiEmbedOut::finish   T % 4 != 0, either kernel: its own nrm[t & 3] pick
      Every row names the trunk path and the drawing site it runs, derived by mirrors of the engine's launch rules (plain_path,
-     draw_site, slices below; the style rows use the style tests' trunk_path), checked against `eng.loop_slices`, and -- where the
+     slices and, for the style rows, trunk_path of tests/plan_mirror.py; draw_site below), checked against `eng.loop_slices`, and -- where the
      loop is one slice of plain kernels -- against the kernel families `profile_read` reports for a profiled run that must equal the
      plain one bit for bit.
   c. one DDPM step in closed form: (sample - posterior mean(x0-hat, x)) / sigma == the ORACLE's normals (not mst_philox_normal's).
@@ -29,6 +29,7 @@ import mst_amd  # noqa: F401
 import mst_amd.synthetic as syn
 from conftest import rel_l2  # noqa: F401  (the modules' common import; every comparison here is exact or absolute)
 from oracle import philox, schedule
+from plan_mirror import SMALL_M, plain_path, slices, trunk_path
 
 pytestmark = pytest.mark.gpu
 SEED = 77
@@ -124,19 +125,6 @@ def test_philox_normal_equals_the_oracle_elementwise(B, F, T):
 
 
 # ------------------------------------------------------------------------------ b. every kernel that draws
-SMALL_M, SMALL_LN_M = 1900, 512          # csrc/mst_engine.hip defaults (MST_SMALL_M, MST_SMALL_LN_M)
-
-
-def plain_path(rows, T, small_m=SMALL_M, precise=False):
-    """Mirror of run_trunk for `rows` transformer rows of T frames (one slice's launch)."""
-    M = rows * (T + 1)
-    if not (precise or (small_m > 0 and M <= small_m)):
-        return "fused-large-tile"
-    if precise or T <= 16:
-        return "small-tile-hi-lo"        # every activation as hi + lo: engine precise mode, or clips of <= 16 frames
-    return "small-launch-ln-in-gemm" if M <= SMALL_LN_M else "small-tile"
-
-
 def draw_site(F, T, cfg, precise=False):
     """Mirror of launch_out_nt / k_embed_out's `staged` / DEpiEmbedOut::finish's `vec`: which caller of philox_normal4 draws."""
     nbw = (F + 127) // 128
@@ -144,27 +132,6 @@ def draw_site(F, T, cfg, precise=False):
     if T % 4:
         return kernel + ":finish-scalar"
     return "k_embed_out:embed-staged" if kernel == "k_embed_out" and nbw <= 3 else kernel + ":finish-vector"
-
-
-def slices(B, T, cfg, streams=0, small_m=SMALL_M, trunk=False, precise=False):
-    """Mirror of loop_slices_for + enqueue_step's split: [(first clip, clips)] per slice."""
-    rows = (2 if cfg else 1) * B
-    M = rows * (T + 1)
-    small_launch = small_m > 0 and M <= small_m
-    n = streams
-    if n == 0 and trunk and (T + 16) // 16 == 13 and not small_launch:
-        n = 1
-    elif n == 0:
-        small = precise or small_launch
-        tiles = (M + 63) // 64
-        waves = (tiles + 255) // 256
-        n = 3 if small else min(waves, 3)
-        if not small and waves == 1 and tiles >= 192:
-            n = 3
-    while n > 1 and rows // n < 8:
-        n -= 1
-    per = -(-B // n)
-    return [(c0, min(per, B - c0)) for c0 in range(0, B, per)]
 
 
 FAMILIES = {"fused-large-tile": {"qkv_attention_fused", "layer_tail_fused"},
@@ -247,7 +214,6 @@ def test_in_kernel_draw_equals_the_same_numbers_injected(c, monkeypatch):
     assert len(sl) == c["nsl"], sl
     mult = 2 if cfg else 1
     if styles:
-        from test_gpu_style_kernels import trunk_path
         paths = {"style:" + trunk_path(mult * nb, T, slices=len(sl)) for _, nb in sl}
     else:
         paths = {plain_path(mult * nb, T, env.get("MST_SMALL_M", SMALL_M), precise) for _, nb in sl}

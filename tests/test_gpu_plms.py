@@ -28,7 +28,8 @@ import mst_amd.synthetic as syn
 import plms_fixture as pf
 from conftest import SEED, rel_l2
 from oracle import denoiser
-from test_gpu_noise import FAMILIES, SMALL_M, TRUNK_FAMILIES, draw_site, mask_of, plain_path, slices
+from plan_mirror import SMALL_M, plain_path, slices
+from test_gpu_noise import FAMILIES, TRUNK_FAMILIES, draw_site, mask_of
 from test_gpu_reverse import (EMB, PE, RSCA, SCA, TOL, VEC, _model, _step_inputs, _xstart64, cu, dev, embeds_next, make, sched, weights,
                               within)
 

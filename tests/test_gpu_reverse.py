@@ -212,7 +212,8 @@ def test_fused_single_steps_vs_the_reference(tag, resp, path):
 
 
 # ------------------------------------------------------------------------------ 3. trajectories on the fused paths
-from test_gpu_noise import FAMILIES, SMALL_M, TRUNK_FAMILIES, draw_site, mask_of, plain_path, slices  # noqa: E402
+from plan_mirror import SMALL_M, plain_path, slices  # noqa: E402
+from test_gpu_noise import FAMILIES, TRUNK_FAMILIES, draw_site, mask_of  # noqa: E402
 
 EMB, VEC, SCA, RSCA = "k_embed_out:embed-staged", "k_gemm_dma:finish-vector", "k_embed_out:finish-scalar", "k_gemm_dma:finish-scalar"
 

@@ -11,7 +11,7 @@ mistake pass.  Here every style's clips of a mixed batch are compared with oracl
   6. sampling loops split into 3 slices (one plan per slice), DDPM with inpainting and a guided DDIM loop;
   7. bitwise invariants: the XCD-affine order equals the plain one; growing 3 -> 8 slots leaves slots 0-2 unchanged.
 
-Each case id names the path it forces, computed by mirrors of the engine's rules (trunk_path, loop_slices below)."""
+Each case id names the path it forces, computed by the mirror of the engine's launch plan (trunk_path, loop_slices of tests/plan_mirror.py)."""
 import zlib
 
 import numpy as np
@@ -21,6 +21,7 @@ import torch
 import mst_amd  # noqa: F401
 from conftest import rel_l2
 import style_fixture as sf
+from plan_mirror import loop_slices, slices_of, trunk_path
 from style_fixture import cu
 
 pytestmark = pytest.mark.gpu
@@ -29,55 +30,6 @@ TOL = 1e-3                              # tests/test_gpu_style_bank.py, per styl
 K = 3
 F_XIA, T_XIA = 181, 76
 F_HML, T_HML = 263, 196
-
-# csrc/mst_engine.hip defaults
-SMALL_M = 1900                          # small_m (MST_SMALL_M): launches of at most this many token rows take the small path
-SMALL_LN_M = 512                        # small_ln_m: ... with the LayerNorms inside the 16-row GEMMs up to this many rows
-NTB1_M, NTB2_FROM = 800, 1300           # g_rows_ntb1_m / g_rows_ntb2_from (MST_SMALL_NTB1_M / MST_SMALL_NTB2_FROM, read at load)
-
-
-def trunk_path(rows, T, small_m=SMALL_M, tail_ntb=0, slices=1):
-    """Mirror of run_trunk_style's choice for `rows` transformer rows of T frames: the small path's GEMM tile height
-    (launch_rows_seg_m) and whether its LayerNorms are fused (lnf) or run by k_ln_rows_style (ln); or the fused path's attention
-    instantiation (launch_qkv_attn2_style) and tail height (launch_tail_style; `slices` = cur_slices of the launch)."""
-    S = T + 1
-    M = rows * S
-    if small_m > 0 and M <= small_m:
-        if M <= SMALL_LN_M:
-            return "small-ntb1-lnf"
-        return f"small-ntb{1 if M <= NTB1_M else 2 if M > NTB2_FROM else 4}-ln"
-    n16 = (S + 15) // 16
-    nt = 13 if n16 == 13 else (n16 + 1) // 2 * 2
-    ntb = tail_ntb
-    if ntb == 0:
-        ntb = 4
-        if slices == 1:
-            if (M + 31) // 32 <= 256:
-                ntb = 2
-            elif (M + 47) // 48 <= 256:
-                ntb = 3
-    return f"fused-nt{nt}-tail{ntb}"
-
-
-def loop_slices(rows, T, small_m=SMALL_M):
-    """Mirror of loop_slices_for (no MST_STREAMS, no resident trunk)."""
-    M = rows * (T + 1)
-    small = small_m > 0 and M <= small_m
-    tiles = (M + 63) // 64
-    waves = (tiles + 255) // 256
-    n = 3 if small else min(waves, 3)
-    if not small and waves == 1 and tiles >= 192:
-        n = 3
-    while n > 1 and rows // n < 8:
-        n -= 1
-    return n
-
-
-def slices_of(B, n):
-    """enqueue_step / style_plan's split of B clips into n slices: [(first clip, clips)]."""
-    per = -(-B // n)
-    return [(c0, min(per, B - c0)) for c0 in range(0, B, per)]
-
 
 def pattern(name, B, k=K):
     if name == "cycle":                  # no two neighbouring clips share a style: a tile holds as many segments as clips it touches
