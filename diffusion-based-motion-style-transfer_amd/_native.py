@@ -59,6 +59,14 @@ SIGNATURES = {
     "mst_sample_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.c_void_p]),
     "mst_sample_loop_plms": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.POINTER(MstPlmsArgs), C.c_void_p]),
     "mst_sample_loop_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.POINTER(MstGuideArgs), C.c_void_p]),
+    "mst_window_max_frames": (C.c_int, []),
+    "mst_window_plan_create": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mst_window_plan_destroy": (None, [C.c_void_p]),
+    "mst_window_plan_set_fold": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mst_window_unfold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mst_window_stitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mst_sample_loop_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.c_void_p, C.c_void_p]),
     "mst_step_epilogue_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32,
                                            C.POINTER(MstGuideArgs), C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -32,6 +32,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_feet.h"
 #include "mst_ik.h"
 #include "mst_encode.h"
+#include "mst_window.h"
 #include "mst_plan.h"
 
 using namespace mst;
@@ -1843,8 +1844,14 @@ static int join_slices(mst_engine* e, const LoopPlan& p) {
 // advances, so the instantiated graph is reused by every replay and by every later call with the same shapes.
 // pl: the PLMS chain state (mst_sample_loop_plms; a->sampler is then MST_SAMPLER_PLMS), null for every other sampler.
 // gd: the guide (mst_sample_loop_guided, which has checked it; MST_SAMPLER_DDPM / MST_SAMPLER_DDIM only), null for an unguided loop.
+// wp: the window plan (mst_sample_loop_windows, which has checked it against the call; MST_SAMPLER_DDIM at eta 0, no guide), null otherwise.
+//     Every step is then enqueued from the host and reads x from memory -- no graph, no chained frame rows, no fused embed: each would
+//     hand step j + 1 rows that the stitch has since changed -- and behind every step the slices join, k_window_stitch runs on the loop
+//     stream and the slices fork again.  With a null plan nothing below differs from what it enqueued before the plan existed.
+static int window_stitch_launch(const mst_window_plan* wp, float* win, int feats, float* long_out, hipStream_t st);
+static float* window_plan_fold(const mst_window_plan* wp);
 static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_plms_args* pl, void* stream,
-                           const mst_guide_args* gd = nullptr) {
+                           const mst_guide_args* gd = nullptr, const mst_window_plan* wp = nullptr) {
     if (!s || !a) return fail("mst_sample_loop: null argument");
     CHECK(check_ready(e, a->batch, a->frames, a->cfg));
     if (a->sampler == MST_SAMPLER_PLMS && !pl)
@@ -1915,7 +1922,7 @@ static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_
     const PlanKnobs knobs = plan_knobs(e);     // ... and every switch the launch plan reads, word by word: a knob added to PlanKnobs is in the key
     key.insert(key.end(), reinterpret_cast<const int*>(&knobs), reinterpret_cast<const int*>(&knobs) + PLAN_KNOB_WORDS);
     const int j0 = warm ? 1 : 0;                              // the warm-up is the call's step 0
-    const bool use_graph = e->graph_on && !e->prof_on && e->dbg_stage < 0 && nrun - j0 >= 2 * U;
+    const bool use_graph = e->graph_on && !wp && !e->prof_on && e->dbg_stage < 0 && nrun - j0 >= 2 * U;
     bool forked = false;
     auto steps = [&]() -> int {
         int j = 0;
@@ -1966,7 +1973,7 @@ static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_
         // the transpose kernel.  Not under CFG (there a slice's rows sit at 2 x its first clip, which changes when an instrumented
         // step runs as one slice), not for frame counts the epilogue walks element-wise, not in captured graphs (their first
         // step would have to differ from call to call).
-        const bool chain = e->fuse_frames && !a->cfg && (a->frames & 3) == 0 && e->dbg_stage < 0;
+        const bool chain = e->fuse_frames && !wp && !a->cfg && (a->frames & 3) == 0 && e->dbg_stage < 0;
         // ... and where the shapes allow, step j's output projection embeds step j + 1 in the same launch (MST_FUSE_EMBED=0: frame rows
         // only).  Instrumented steps and their neighbours keep the two kernels apart, so that the event-timed families stay what they say.
         const bool fuse_embed = chain && e->fuse_embed && embed_next_fits(e, a->frames);
@@ -1982,6 +1989,10 @@ static int sample_loop_run(mst_engine* e, const mst_schedule* s, const mst_loop_
             const bool embed_next = fuse_embed && j + 1 < nrun && !instrumented(j) && !instrumented(j + 1);
             CHECK(enqueue_step(e, p, j, nsj, chain && j > j0 && !stream_ready, chain && j + 1 < nrun && !embed_next, stream_ready, embed_next));
             stream_ready = embed_next;
+            if (wp) {      // the windows' shared frames -> one value each, on the loop stream behind every slice; the last stitch is the fold
+                if (forked) { CHECK(join_slices(e, p)); forked = false; }
+                CHECK(window_stitch_launch(wp, a->x_dev, e->cfg.feats, j + 1 == nrun ? window_plan_fold(wp) : nullptr, st));
+            }
         }
         return 0;
     };
@@ -2044,6 +2055,146 @@ extern "C" int mst_sample_loop_guided(mst_engine* e, const mst_schedule* s, cons
     if (g->kind == MST_GUIDE_GRADIENT && a->t_start != a->t_end)
         return fail("mst_sample_loop_guided: MST_GUIDE_GRADIENT carries the gradient of ONE step: t_start %d must equal t_end %d", a->t_start, a->t_end);
     return sample_loop_run(e, s, a, nullptr, stream, g);
+}
+
+// ------------------------------------------------------------------------------------------ windows ABI (mst_window.h)
+// One plan = the cut of `clips` long clips [C,F,1,L] into `windows` windows [N,F,1,W]; the feature count is a call's, not the plan's.
+struct mst_window_plan {
+    int device = 0, clips = 0, windows = 0, window = 0, long_frames = 0;
+    int* dev = nullptr;                      // ONE allocation: clip_len [C] | win_clip [N] | win_start [N] | cover [C * L] {first, count}
+    const int *clip_len = nullptr, *win_clip = nullptr, *win_start = nullptr;
+    const WinCover* cover = nullptr;
+    float* fold_dev = nullptr;               // mst_window_plan_set_fold: where mst_sample_loop_windows' last stitch writes the long clips
+};
+
+extern "C" int mst_window_max_frames(void) { return kWinMaxFrames; }
+
+extern "C" int mst_window_plan_create(const int32_t* clip_len, const int32_t* clip_win0, const int32_t* win_start, int32_t clips, int32_t windows,
+                                      int32_t window, int32_t long_frames, int32_t device, mst_window_plan** out) {
+    const char* who = "mst_window_plan_create";
+    if (!clip_len || !clip_win0 || !win_start || !out) return fail("%s: null argument", who);
+    if (clips < 1 || windows < clips) return fail("%s: %d windows for %d clips (every clip has at least one window)", who, windows, clips);
+    if (window < 1) return fail("%s: window %d must be at least 1 frame", who, window);
+    if (long_frames < 1 || long_frames > kWinMaxFrames)
+        return fail("%s: long_frames %d outside 1..%d (mst_window_max_frames)", who, long_frames, kWinMaxFrames);
+    if (clip_win0[0] != 0 || clip_win0[clips] != windows)
+        return fail("%s: clip_win0 must run from 0 to the window count %d (got %d .. %d)", who, windows, clip_win0[0], clip_win0[clips]);
+    std::vector<int> host((size_t)clips + 2 * (size_t)windows + 2 * (size_t)clips * long_frames, 0);
+    int* const h_len = host.data();
+    int* const h_clip = h_len + clips;
+    int* const h_start = h_clip + windows;
+    WinCover* const h_cov = reinterpret_cast<WinCover*>(h_start + windows);
+    for (int c = 0; c < clips; c++) {
+        const int len = clip_len[c], n0 = clip_win0[c], n1 = clip_win0[c + 1];
+        if (len < 1 || len > long_frames) return fail("%s: clip %d: length %d outside 1..long_frames %d", who, c, len, long_frames);
+        if (n1 <= n0 || n1 > windows) return fail("%s: clip %d: clip_win0 %d .. %d names no window (it must ascend, within %d windows)", who, c, n0, n1, windows);
+        const int reach = len > window ? len : window;      // a clip no longer than the window: one window at 0, zero padding behind the clip
+        int covered = 0;                                    // frames [0, covered) are covered by the windows seen so far
+        for (int n = n0; n < n1; n++) {
+            const int st = win_start[n];
+            if (st < 0) return fail("%s: clip %d: window %d starts at %d (negative)", who, c, n, st);
+            if (n > n0 && st <= win_start[n - 1])
+                return fail("%s: clip %d: window starts must be strictly ascending (window %d starts at %d behind %d)", who, c, n, st, win_start[n - 1]);
+            if ((long long)st + window > reach)
+                return fail("%s: clip %d: window %d covers frames %d .. %d past max(length %d, window %d): start + W <= max(len, W)", who, c, n, st,
+                            st + window - 1, len, window);
+            if (st > covered) return fail("%s: clip %d: uncovered frame %d (window %d starts at %d)", who, c, covered, n, st);
+            covered = st + window;
+            h_clip[n] = c;
+            h_start[n] = st;
+        }
+        if (covered < len) return fail("%s: clip %d: uncovered frame %d (the last window ends there, the clip is %d frames long)", who, c, covered, len);
+        h_len[c] = len;
+        // the covering run of every frame below the length: both ends only move forward
+        int lo = n0, hi = n0;                               // windows [lo, hi) cover f
+        for (int f = 0; f < len; f++) {
+            while (hi < n1 && win_start[hi] <= f) hi++;
+            while (lo < hi && win_start[lo] + window <= f) lo++;
+            h_cov[(size_t)c * long_frames + f] = WinCover{lo, hi - lo};
+        }
+    }
+    ON_DEVICE(device);
+    mst_window_plan* p = new mst_window_plan();
+    p->device = device; p->clips = clips; p->windows = windows; p->window = window; p->long_frames = long_frames;
+    if (hipMalloc(&p->dev, host.size() * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        delete p;
+        return fail("%s: out of device memory (%zu bytes) or no device %d", who, host.size() * sizeof(int), device);
+    }
+    if (hipMemcpy(p->dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {      // the one upload
+        (void)hipGetLastError();
+        (void)hipFree(p->dev);
+        delete p;
+        return fail("%s: the upload of the plan failed", who);
+    }
+    p->clip_len = p->dev;
+    p->win_clip = p->dev + clips;
+    p->win_start = p->win_clip + windows;
+    p->cover = reinterpret_cast<const WinCover*>(p->win_start + windows);
+    *out = p;
+    return 0;
+}
+
+extern "C" void mst_window_plan_destroy(mst_window_plan* p) {
+    if (!p) return;
+    DeviceGuard g(p->device);
+    if (p->dev) (void)hipFree(p->dev);
+    delete p;
+}
+
+extern "C" int mst_window_plan_set_fold(mst_window_plan* p, float* long_out_dev) {
+    if (!p) return fail("mst_window_plan_set_fold: null plan");
+    p->fold_dev = long_out_dev;
+    return 0;
+}
+static float* window_plan_fold(const mst_window_plan* wp) { return wp->fold_dev; }
+
+static int window_blocks(const char* who, size_t elems, unsigned* blocks) {
+    const size_t b = (elems + kWinThreads - 1) / kWinThreads;
+    if (b > 0x7fffffffu) return fail("%s: %zu elements are more than one launch takes", who, elems);
+    *blocks = (unsigned)b;
+    return 0;
+}
+
+extern "C" int mst_window_unfold(const mst_window_plan* p, const float* long_dev, int32_t feats, float* win_dev, void* stream) {
+    if (!p || !long_dev || !win_dev) return fail("mst_window_unfold: null argument");
+    if (feats < 1) return fail("mst_window_unfold: feats %d must be at least 1", feats);
+    unsigned blocks = 0;
+    CHECK(window_blocks("mst_window_unfold", (size_t)p->windows * feats * p->window, &blocks));
+    ON_DEVICE(p->device);
+    hipLaunchKernelGGL(k_window_unfold, dim3(blocks), dim3(kWinThreads), 0, (hipStream_t)stream, long_dev, p->clip_len, p->win_clip, p->win_start,
+                       p->windows, feats, p->window, p->long_frames, win_dev);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+static int window_stitch_launch(const mst_window_plan* p, float* win, int feats, float* long_out, hipStream_t st) {
+    unsigned blocks = 0;
+    CHECK(window_blocks("mst_window_stitch", (size_t)p->clips * feats * p->long_frames, &blocks));
+    hipLaunchKernelGGL(k_window_stitch, dim3(blocks), dim3(kWinThreads), 0, st, win, p->cover, p->win_start, p->clips, feats, p->window,
+                       p->long_frames, long_out);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_window_stitch(const mst_window_plan* p, float* win_dev, int32_t feats, float* long_out_dev, void* stream) {
+    if (!p || !win_dev) return fail("mst_window_stitch: null argument");
+    if (feats < 1) return fail("mst_window_stitch: feats %d must be at least 1", feats);
+    ON_DEVICE(p->device);
+    return window_stitch_launch(p, win_dev, feats, long_out_dev, (hipStream_t)stream);
+}
+
+// ddim_sample_loop over every window of every long clip as ONE batch, stitched behind every step (sample_loop_run with a plan).
+extern "C" int mst_sample_loop_windows(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_window_plan* p, void* stream) {
+    const char* who = "mst_sample_loop_windows";
+    if (!e || !s || !a || !p) return fail("%s: null argument", who);
+    if (a->sampler != MST_SAMPLER_DDIM)
+        return fail("%s: sampler %d is not MST_SAMPLER_DDIM: only the deterministic DDIM step keeps the windows' shared frames identical", who, a->sampler);
+    if (a->eta != 0.0f) return fail("%s: eta %g must be 0: a stochastic step would need per-window noise unfolded from one long draw", who, (double)a->eta);
+    if (a->batch != p->windows) return fail("%s: batch %d is not the plan's window count %d", who, a->batch, p->windows);
+    if (a->frames != p->window) return fail("%s: frames %d is not the plan's window %d", who, a->frames, p->window);
+    if (p->device != e->cfg.device) return fail("%s: the plan lives on device %d, the engine on device %d", who, p->device, e->cfg.device);
+    return sample_loop_run(e, s, a, nullptr, stream, nullptr, p);
 }
 
 // ------------------------------------------------------------------------------------------ elementwise ABI

@@ -657,6 +657,110 @@ class GaussianDiffusion:
             final = out
         return dump if dump_all_xstart else final["sample"]
 
+    # -- Clips of any length (no reference counterpart; diffusion/windows.py): overlapping windows of the model's own
+    #    length, all windows of all clips as one batch, their shared frames stitched behind every step.
+    def ddim_sample_loop_windows(self, model, shape=None, plan=None, window=None, overlap=None, lengths=None, noise=None,
+                                 clip_denoised=True, model_kwargs=None, skip_timesteps=0, init_image=None, eta=0.0, progress=False,
+                                 dump_all_xstart=False, return_windows=False, cond_fn=None, denoised_fn=None, device=None):
+        """ddim_sample_loop on long clips [C,F,1,L] (`shape`, or None: the shape of `noise` / `init_image`), L up to 4096.
+        plan: a `windows.WindowPlan`, or None: built from `lengths` (default: y['lengths'], else L for every clip), `window` and
+        `overlap`.  Everything elementwise happens once on the long tensors -- the draw of x_T, q_sample of `init_image` under the long
+        inpainting mask -- and the result is unfolded; the long y['inpainted_motion'] / y['inpainting_mask'] are unfolded, the per-clip
+        y entries (text, text_embed, scale, style) are gathered per window, y['lengths'] / y['mask'] come from the plan.
+        Returns the long sample [C,F,1,L] (exactly 0.0 from a clip's length on), or with dump_all_xstart the list of folded x0-hat
+        tensors, one per step; with return_windows a pair (that, the windows [N,F,1,W] as the last stitch left them).
+        Deterministic DDIM only: for eta == 0 x_{t-1} is linear in x_t and x0-hat, so windows that start from one long x_T hold identical
+        values on shared frames after every stitch.  Refused (ValueError): eta != 0, cond_fn, denoised_fn, a model that is not the
+        native denoiser in eval mode predicting x_start, a window above engine.MAX_FRAMES."""
+        from . import windows as _win
+        if eta != 0.0:
+            raise ValueError(f"ddim_sample_loop_windows: eta {eta} must be 0 (a stochastic step would need per-window noise unfolded "
+                             "from one long draw)")
+        if cond_fn is not None:
+            raise ValueError("ddim_sample_loop_windows: cond_fn is not supported (guided windowed loops are not built)")
+        if denoised_fn is not None:
+            raise ValueError("ddim_sample_loop_windows: denoised_fn is not supported (it would run between the step and the stitch)")
+        denoiser, cfg, _ = _unwrap(model)
+        if denoiser is None:
+            raise ValueError("ddim_sample_loop_windows: the model is not the native denoiser (no mst_engine): the windowed loop "
+                             "runs inside the library only")
+        if denoiser.training:
+            raise ValueError("ddim_sample_loop_windows: the model is in training mode; call .eval()")
+        if self.model_mean_type != ModelMeanType.START_X:
+            raise ValueError("ddim_sample_loop_windows: the native loop predicts x_start only")
+        if shape is None:
+            src = noise if noise is not None else init_image
+            if src is None:
+                raise ValueError("ddim_sample_loop_windows: shape is None and neither noise nor init_image gives one")
+            shape = tuple(src.shape)
+        shape = tuple(int(v) for v in shape)
+        if len(shape) != 4 or shape[2] != 1:
+            raise ValueError(f"ddim_sample_loop_windows: shape {shape} is not (C, F, 1, L)")
+        device = self._loop_device(model, device)
+        y = dict(self._y(model_kwargs))
+        if plan is None:
+            if window is None or overlap is None:
+                raise ValueError("ddim_sample_loop_windows: pass a plan, or window and overlap")
+            if lengths is None:
+                lengths = y.get('lengths')
+            if lengths is None:
+                lengths = [shape[3]] * shape[0]
+            if int(window) > _eng.MAX_FRAMES:
+                raise ValueError(f"ddim_sample_loop_windows: window {int(window)} is above the engine's limit of {_eng.MAX_FRAMES} frames")
+            plan = _win.WindowPlan(lengths, window, overlap, device, long_frames=shape[3])
+        if plan.window > _eng.MAX_FRAMES:
+            raise ValueError(f"ddim_sample_loop_windows: window {plan.window} is above the engine's limit of {_eng.MAX_FRAMES} frames")
+        if (plan.n_clips, plan.long_frames) != (shape[0], shape[3]):
+            raise ValueError(f"ddim_sample_loop_windows: the plan is for {plan.n_clips} clips of {plan.long_frames} frames, "
+                             f"the shape {shape} is not")
+        # x_T, and q_sample of the init image, ONCE on the long tensors (the inpainting variant's noise mask is the long mask)
+        device, img, indices = self._loop_setup(model, shape, noise, device, skip_timesteps, init_image, None, model_kwargs)
+        x = _win.unfold(img.to(device=device, dtype=th.float32).contiguous(), plan)
+        wc = plan.win_clip_tensor()
+        for k in ('inpainted_motion', 'inpainting_mask'):
+            if k in y:
+                y[k] = _win.unfold(_eng._operand(y[k], shape, k, _eng.RULE_BROADCAST, device), plan)
+        if y.get('text') is not None:
+            y['text'] = [y['text'][int(c)] for c in plan.win_clip]
+        for k in ('text_embed', 'scale', 'style'):
+            v = y.get(k)
+            if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == plan.n_clips:
+                y[k] = v[wc.to(v.device)]
+            elif v is not None and not isinstance(v, th.Tensor) and np.ndim(v) >= 1 and len(v) == plan.n_clips:
+                y[k] = th.as_tensor(np.asarray(v))[wc.cpu()]
+        y['lengths'] = th.from_numpy(plan.win_lengths.astype(np.int64)).to(device)
+        y['mask'] = (th.arange(plan.window, device=device)[None, :] < y['lengths'][:, None])[:, None, None, :]
+        kw = dict(model_kwargs or {})
+        kw['y'] = y
+        eng = denoiser.mst_engine(plan.n_windows * (2 if cfg is not None else 1), plan.window)
+        denoiser.mst_prepare(eng, y, cfg is not None)
+        mask, motion = self._inpaint_pair(kw)
+        nmask = self._noise_mask(kw)
+        scale = y['scale'] if cfg is not None else None
+        sch = self._schedule(x.device)
+        out_long = th.empty(shape, dtype=th.float32, device=x.device)
+        # one native call, or with the x0-hat dump chunks bounded like the other loops' ([steps, N, F, 1, W] at once otherwise)
+        chunk = len(indices) if not dump_all_xstart else max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
+        it = range(0, len(indices), chunk)
+        if progress:
+            from tqdm.auto import tqdm
+            it = tqdm(it)
+        dumps = []
+        for c0 in it:
+            idx = indices[c0:c0 + chunk]
+            last = c0 + chunk >= len(indices)
+            res = eng.sample_loop_windows(sch, x, plan, idx[0], idx[-1], cfg=cfg is not None, scale=scale,
+                                          mask=mask if mask is not None else nmask, motion=motion, mask_noise=nmask is not None,
+                                          clip_denoised=clip_denoised, dump_xstart=bool(dump_all_xstart),
+                                          fold_out=out_long if last else None)
+            if dump_all_xstart:
+                for j in range(len(idx)):      # the windows' x0-hat differ on shared frames: each step's dump is stitched into one long tensor
+                    lng = th.empty_like(out_long)
+                    _win.stitch_(res[1][j], plan, long_out=lng)
+                    dumps.append(lng)
+        result = dumps if dump_all_xstart else out_long
+        return (result, x) if return_windows else result
+
     # -- DDIM inversion and its decode half.  The reference has the step (ddim_reverse_sample) and no loop around it: these entries
     #    are additions (INTEGRATION.md).
     def _reverse_loop(self, model, x_start, num_steps, clip_denoised, model_kwargs, device, progress, chunked, want_xstart):

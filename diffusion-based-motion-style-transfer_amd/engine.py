@@ -15,6 +15,7 @@ SAMPLER_DDIM_REVERSE = 2        # x_t -> x_{t+1}, the deterministic DDIM step ru
 SAMPLER_PLMS = 3                # plms_sample (gaussian_diffusion.py:1084-1166): Pseudo Linear Multistep, orders 1..4; no noise term.
                                 # It carries a history, so it runs through sample_loop_plms / Schedule.plms_step, not sample_loop / step
 NOISE_BUFFER, NOISE_PHILOX = 0, 1
+MAX_FRAMES = 223                # longest clip one engine takes (mst_engine_create); longer clips are sampled as overlapping windows (diffusion/windows.py)
 GUIDE_GRADIENT, GUIDE_TARGET = 1, 2    # enum MST_GUIDE_*: a caller's gradient for one step / the target guide computed in the step kernel
 
 # Largest classifier-free guidance factor (the larger of s and 1 - s per clip) at which the default f16-operand path was measured to
@@ -618,6 +619,46 @@ class DenoiserEngine:
             keep.append(guide[1])
         else:
             N.check(N.lib().mst_sample_loop(self.handle, schedule.handle, C.byref(a), N.stream_ptr(self.device)))
+        self._loop_keepalive = keep
+        return (x, dump) if dump_xstart else x
+
+    def sample_loop_windows(self, schedule, x, plan, t_start, t_end=0, cfg=False, scale=None, mask=None, motion=None, mask_noise=True,
+                            clip_denoised=False, dump_xstart=False, fold_out=None):
+        """The deterministic DDIM loop (eta 0) over the windows `x` ([N,F,1,W], in place) of a `windows.WindowPlan`, stitched behind
+        every step (mst_sample_loop_windows): equal, bit for bit, to one-step `sample_loop` calls with `windows.stitch_` between them.
+        fold_out: a [C,F,1,L] float32 tensor the last stitch also writes the long clips into (None: no fold).  Nothing is drawn.
+        Returns x (and the [nsteps,N,F,1,W] x0-hat dump of the windows, as the steps wrote it, when requested)."""
+        assert _need_gpu(x, "x").dtype == torch.float32 and x.is_contiguous()
+        if cfg:
+            self.check_guidance_scale(scale)
+        B, F, one, T = x.shape
+        nsteps = abs(t_start - t_end) + 1
+        a = N.MstLoopArgs()
+        a.batch, a.frames, a.cfg, a.sampler = B, T, int(bool(cfg)), SAMPLER_DDIM
+        a.mask_noise, a.clip_denoised = int(bool(mask_noise)), int(bool(clip_denoised))
+        a.t_start, a.t_end, a.eta = int(t_start), int(t_end), 0.0
+        a.noise_mode, a.seed = NOISE_PHILOX, 0              # sigma is 0 at eta 0: the draw is multiplied away
+        keep = []
+        mask, motion = _mask_pair(mask, motion, x.shape, self.device)
+        scale = None if scale is None else _operand(scale, (B,), "scale", RULE_SCALE, self.device)
+        for name, val in (("scale_dev", scale), ("inpainting_mask_dev", mask), ("inpainted_motion_dev", motion)):
+            if val is not None:
+                keep.append(val)
+                setattr(a, name, val.data_ptr())
+        a.x_dev = x.data_ptr()
+        dump = None
+        if dump_xstart:
+            dump = torch.empty((nsteps,) + tuple(x.shape), dtype=torch.float32, device=self.device)
+            a.xstart_dump_dev = dump.data_ptr()
+        if fold_out is not None:
+            want = (plan.n_clips, F, one, plan.long_frames)
+            assert fold_out.is_cuda and fold_out.dtype == torch.float32 and fold_out.is_contiguous() and tuple(fold_out.shape) == want, \
+                f"fold_out: a contiguous float32 {want} tensor"
+        N.check(N.lib().mst_window_plan_set_fold(plan.handle, N.ptr(fold_out)))
+        try:
+            N.check(N.lib().mst_sample_loop_windows(self.handle, schedule.handle, C.byref(a), plan.handle, N.stream_ptr(self.device)))
+        finally:
+            N.check(N.lib().mst_window_plan_set_fold(plan.handle, None))
         self._loop_keepalive = keep
         return (x, dump) if dump_xstart else x
 

@@ -235,6 +235,44 @@ typedef struct mst_guide_args {
 } mst_guide_args;
 int mst_sample_loop_guided(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_guide_args* g, void* stream);
 
+/* -----------------------------------------------------------------------------------------
+ * Clips of any length: overlapping windows, stitched behind every step (csrc/mst_window.h).  No reference counterpart: the reference
+ * cuts the content clip at max_frames (sample/demo_style_transfer.py:37-38, :184).  The feature rows are frame-local (root velocities,
+ * everything else relative to the root), so rows [s, s + W) of a long clip are the rows of the sub-clip; a long clip [C,F,1,L] is cut
+ * into windows [N,F,1,W] of the model's own length, all windows of all clips are sampled as one batch, and after every step the frames
+ * that two or more windows share are replaced, in all of them, by one weighted mean.
+ * The plan (host arrays, uploaded once by mst_window_plan_create): clip c is clip_len[c] frames long and owns windows
+ * clip_win0[c] .. clip_win0[c + 1] - 1 (clip_win0 has clips + 1 entries, 0 .. windows); window n covers long frames
+ * win_start[n] .. win_start[n] + window - 1 of its clip.  A clip no longer than the window has one window at 0 (frames from its length
+ * on are zero padding).  Refused, each by name: a clip length outside 1 .. long_frames; long_frames above mst_window_max_frames()
+ * (4096, what the stages around the sampler take); a clip without a window; starts that are negative or not strictly ascending;
+ * start + window > max(length, window); an uncovered frame below the length.
+ *   mst_window_unfold   long_dev [C,F,1,L] -> win_dev [N,F,1,W]; window frames at or past the clip's length get 0.0.
+ *   mst_window_stitch   win_dev in place.  Per (clip, feature, long frame), K = the covering windows in ascending order: |K| == 1: not
+ *                       touched; all of K hold the same bits: kept (inpainted rows stay bit-exact); otherwise
+ *                       v = (sum_K h x) / (sum_K h) with h(i) = min(i + 1, W - i) at local frame i, in fp32 in ascending window order,
+ *                       stored into every window of K.  long_out_dev != NULL: also the fold, [C,F,1,L] -- the single covering value or
+ *                       v below the clip's length, exactly 0.0 from there on.  One thread per element, no atomics.
+ *   mst_sample_loop_windows   mst_sample_loop on the N windows with a stitch behind every step: the slice streams join, the stitch runs
+ *                       on the loop stream, the slices fork again.  Every step is enqueued from the host and reads x from memory (no graph
+ *                       replay, no chained frame rows, no fused embed: each would hand the next step rows the stitch has since changed),
+ *                       so an n-step call equals n one-step mst_sample_loop calls with mst_window_stitch between them, bit for bit.
+ *                       The last stitch also writes the long clips where mst_window_plan_set_fold has named a buffer (NULL: no fold).
+ *                       Refused, each by name: any sampler but MST_SAMPLER_DDIM; eta != 0 (for the deterministic step x_{t-1} is linear
+ *                       in x_t and x0-hat, so windows that start from one long x_T hold identical values on shared frames after every
+ *                       stitch, and the mean is a mean over x0-hat alone); batch != the plan's windows; frames != the plan's window; a
+ *                       plan on another device.  It takes no guide: guided windowed loops are not built.
+ * ----------------------------------------------------------------------------------------- */
+typedef struct mst_window_plan mst_window_plan;
+int  mst_window_max_frames(void);
+int  mst_window_plan_create(const int32_t* clip_len, const int32_t* clip_win0, const int32_t* win_start, int32_t clips, int32_t windows,
+                            int32_t window, int32_t long_frames, int32_t device, mst_window_plan** out);
+void mst_window_plan_destroy(mst_window_plan* p);
+int  mst_window_plan_set_fold(mst_window_plan* p, float* long_out_dev);
+int  mst_window_unfold(const mst_window_plan* p, const float* long_dev, int32_t feats, float* win_dev, void* stream);
+int  mst_window_stitch(const mst_window_plan* p, float* win_dev, int32_t feats, float* long_out_dev, void* stream);
+int  mst_sample_loop_windows(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_window_plan* p, void* stream);
+
 /* Number of independent clip slices (1..3) mst_sample_loop runs on separate streams for this
  * batch of `frames`-frame clips (frames <= 0: the engine's max_frames; the policy depends on the
  * token-row count, so pass the loop's own frame count when it is below the cap): clips never interact (no cross-sample op in
