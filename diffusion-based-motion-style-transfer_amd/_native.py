@@ -67,6 +67,8 @@ SIGNATURES = {
     "mst_window_unfold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mst_window_stitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mst_sample_loop_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.c_void_p, C.c_void_p]),
+    "mst_window_noise": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mst_window_sample_loop": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MstLoopArgs), C.c_void_p, C.POINTER(MstGuideArgs), C.c_void_p]),
     "mst_step_epilogue_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32,
                                            C.POINTER(MstGuideArgs), C.c_void_p, C.c_void_p, C.c_void_p]),

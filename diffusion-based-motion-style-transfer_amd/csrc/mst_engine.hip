@@ -1844,7 +1844,9 @@ static int join_slices(mst_engine* e, const LoopPlan& p) {
 // advances, so the instantiated graph is reused by every replay and by every later call with the same shapes.
 // pl: the PLMS chain state (mst_sample_loop_plms; a->sampler is then MST_SAMPLER_PLMS), null for every other sampler.
 // gd: the guide (mst_sample_loop_guided, which has checked it; MST_SAMPLER_DDPM / MST_SAMPLER_DDIM only), null for an unguided loop.
-// wp: the window plan (mst_sample_loop_windows, which has checked it against the call; MST_SAMPLER_DDIM at eta 0, no guide), null otherwise.
+// wp: the window plan, null otherwise.  mst_sample_loop_windows (MST_SAMPLER_DDIM at eta 0, no guide) and mst_window_sample_loop
+//     (MST_SAMPLER_DDPM, or MST_SAMPLER_DDIM at any eta, with or without gd; a step with a noise term reads buffer noise that
+//     mst_window_noise drew in long-clip coordinates) have checked it against the call.
 //     Every step is then enqueued from the host and reads x from memory -- no graph, no chained frame rows, no fused embed: each would
 //     hand step j + 1 rows that the stitch has since changed -- and behind every step the slices join, k_window_stitch runs on the loop
 //     stream and the slices fork again.  With a null plan nothing below differs from what it enqueued before the plan existed.
@@ -2195,6 +2197,52 @@ extern "C" int mst_sample_loop_windows(mst_engine* e, const mst_schedule* s, con
     if (a->frames != p->window) return fail("%s: frames %d is not the plan's window %d", who, a->frames, p->window);
     if (p->device != e->cfg.device) return fail("%s: the plan lives on device %d, the engine on device %d", who, p->device, e->cfg.device);
     return sample_loop_run(e, s, a, nullptr, stream, nullptr, p);
+}
+
+// The noise of stochastic windowed steps, drawn in long-clip coordinates (k_window_noise): out [nsteps,N,F,1,W], entry j =
+// unfold(mst_philox_normal(C, F, L, seed, step0 + j)) -- what an MST_NOISE_BUFFER loop of mst_window_sample_loop reads.
+extern "C" int mst_window_noise(const mst_window_plan* p, int32_t feats, uint64_t seed, uint32_t step0, int32_t nsteps, float* out_dev,
+                                void* stream) {
+    const char* who = "mst_window_noise";
+    if (feats < 1) return fail("%s: feats %d must be at least 1", who, feats);
+    if (nsteps < 1) return fail("%s: nsteps %d must be at least 1", who, nsteps);
+    if (!p) return fail("%s: null plan", who);
+    if (!out_dev) return fail("%s: null out", who);
+    const int quads = ((p->long_frames > p->window ? p->long_frames : p->window) + 3) / 4;
+    unsigned blocks = 0;
+    CHECK(window_blocks(who, (size_t)nsteps * p->clips * feats * quads, &blocks));
+    ON_DEVICE(p->device);
+    hipLaunchKernelGGL(k_window_noise, dim3(blocks), dim3(kWinThreads), 0, (hipStream_t)stream, p->cover, p->clip_len, p->win_start, p->clips,
+                       p->windows, feats, p->window, p->long_frames, quads, nsteps, (unsigned long long)seed, (unsigned)step0, out_dev);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// p_sample_loop / ddim_sample_loop (any eta), with or without a guide, over every window of every long clip as ONE batch, stitched
+// behind every step: mst_sample_loop_windows (which stays the deterministic subset, refusals included) extended by the noise term and
+// by mst_sample_loop_guided's guide.
+extern "C" int mst_window_sample_loop(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_window_plan* p,
+                                      const mst_guide_args* g, void* stream) {
+    const char* who = "mst_window_sample_loop";
+    if (!e || !s || !a || !p) return fail("%s: null argument", who);
+    if (a->sampler != MST_SAMPLER_DDPM && a->sampler != MST_SAMPLER_DDIM)
+        return fail("%s: sampler %d is neither MST_SAMPLER_DDPM nor MST_SAMPLER_DDIM: PLMS and the reverse DDIM step over windows are not built",
+                    who, a->sampler);
+    if (a->sampler == MST_SAMPLER_DDPM || a->eta != 0.0f) {      // the step has a noise term
+        if (a->noise_mode == MST_NOISE_PHILOX)
+            return fail("%s: MST_NOISE_PHILOX with a noise term: the in-kernel draw is keyed by window, so windows that share a long frame "
+                        "would draw different numbers for it; fill a buffer with mst_window_noise and pass MST_NOISE_BUFFER", who);
+        if (!a->noise_dev) return fail("%s: noise buffer missing (mst_window_noise fills one)", who);
+    }
+    if (a->batch != p->windows) return fail("%s: batch %d is not the plan's window count %d", who, a->batch, p->windows);
+    if (a->frames != p->window) return fail("%s: frames %d is not the plan's window %d", who, a->frames, p->window);
+    if (p->device != e->cfg.device) return fail("%s: the plan lives on device %d, the engine on device %d", who, p->device, e->cfg.device);
+    if (g) {
+        CHECK(guide_check(who, s, a->sampler, g));
+        if (g->kind == MST_GUIDE_GRADIENT && a->t_start != a->t_end)
+            return fail("%s: MST_GUIDE_GRADIENT carries the gradient of ONE step: t_start %d must equal t_end %d", who, a->t_start, a->t_end);
+    }
+    return sample_loop_run(e, s, a, nullptr, stream, g, p);
 }
 
 // ------------------------------------------------------------------------------------------ elementwise ABI

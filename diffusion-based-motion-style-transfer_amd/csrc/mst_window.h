@@ -21,8 +21,17 @@
 // Lanes walk long frames, so a wavefront reads and writes 64 consecutive floats of each covering window and of the long row.  Window
 // starts are arbitrary: a 16-byte access along frames would be legal only where start, W and L are all multiples of 4, which the last
 // window of a clip (start = len - W) almost never is; the kernels are dword-per-lane at every shape instead of carrying two paths.
+//
+// k_window_noise: the noise of a stochastic step (ancestral, or DDIM at eta != 0) in LONG-clip coordinates.  The step kernels' own draw
+// is keyed by (frame quad, feature, batch clip, step) of the WINDOW, so two windows would draw different numbers for a long frame they
+// share and the stitch's mean would shrink the noise variance there.  Here entry j of the buffer is unfold(Z_j), Z_j [C,F,1,L] =
+// mst_philox_normal(C, F, L, seed, step0 + j): element (c, f, l) is component l & 3 of philox_normal4(l >> 2, f, c, step0 + j, seed),
+// the code the in-kernel draw shares.  Every window that covers a long frame receives the same bits for it, x_{t-1} stays linear in
+// (x_t, x0-hat, noise), and the stitch stays the exact bookkeeping it is for eta == 0.  One thread owns one long quad of one step: it
+// draws once and scatters the four normals to the covering windows through the cover table, a dword at a time.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "mst_common.h"
 
 namespace mst {
 
@@ -82,6 +91,38 @@ k_window_stitch(float* __restrict__ win, const WinCover* __restrict__ cover, con
         }
     }
     if (lng) lng[idx] = v;
+}
+
+// noise [nsteps,N,F,1,W] <- unfold of the long draws Z_j [C,F,1,L], j = 0 .. nsteps - 1; EVERY element is written (the buffer may be
+// uninitialised): window frames at or past the clip's length get 0.0.  Such frames exist only in the single window, at start 0, of a clip
+// shorter than W, and W may exceed L, so a row is walked in Q = ceil(max(L, W) / 4) quads: frames from L on have no long element and
+// are padding.  A quad at or past the clip's length draws nothing.
+__global__ void __launch_bounds__(kWinThreads)
+k_window_noise(const WinCover* __restrict__ cover, const int* __restrict__ clip_len, const int* __restrict__ win_start, int C, int N, int F,
+               int W, int L, int Q, int nsteps, unsigned long long seed, unsigned step0, float* __restrict__ out) {
+    const size_t idx = (size_t)blockIdx.x * kWinThreads + threadIdx.x;
+    if (idx >= (size_t)nsteps * C * F * Q) return;
+    const int q = (int)(idx % Q);
+    size_t row = idx / Q;                    // (j * C + c) * F + feat
+    const int feat = (int)(row % F);
+    row /= F;
+    const int c = (int)(row % C), j = (int)(row / C);
+    const int len = clip_len[c];
+    float* const step = out + (size_t)j * N * F * W;
+    const WinCover* const cov = cover + (size_t)c * L;
+    float n[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (4 * q < len) philox_normal4((unsigned)q, (unsigned)feat, (unsigned)c, step0 + (unsigned)j, seed, n);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int l = 4 * q + k;
+        if (l < len) {                       // (len <= L: the cover entry exists; its windows hold l at local frame l - start, in [0, W))
+            const WinCover kc = cov[l];
+            for (int w = 0; w < kc.count; w++)
+                step[((size_t)(kc.first + w) * F + feat) * W + (l - win_start[kc.first + w])] = n[k];
+        } else if (l < W && len < W) {       // padding of the clip's only window (frame 0 is always covered, by the clip's first window)
+            step[((size_t)cov[0].first * F + feat) * W + l] = 0.0f;
+        }
+    }
 }
 
 }  // namespace mst

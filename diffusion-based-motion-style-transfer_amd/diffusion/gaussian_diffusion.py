@@ -670,48 +670,78 @@ class GaussianDiffusion:
         Returns the long sample [C,F,1,L] (exactly 0.0 from a clip's length on), or with dump_all_xstart the list of folded x0-hat
         tensors, one per step; with return_windows a pair (that, the windows [N,F,1,W] as the last stitch left them).
         Deterministic DDIM only: for eta == 0 x_{t-1} is linear in x_t and x0-hat, so windows that start from one long x_T hold identical
-        values on shared frames after every stitch.  Refused (ValueError): eta != 0, cond_fn, denoised_fn, a model that is not the
-        native denoiser in eval mode predicting x_start, a window above engine.MAX_FRAMES."""
-        from . import windows as _win
+        values on shared frames after every stitch (`sample_loop_windows` / `p_sample_loop_windows` take eta, the ancestral step and a
+        cond_fn).  Refused (ValueError): eta != 0, cond_fn, denoised_fn, a model that is not the native denoiser in eval mode
+        predicting x_start, a window above engine.MAX_FRAMES."""
+        who = "ddim_sample_loop_windows"
         if eta != 0.0:
-            raise ValueError(f"ddim_sample_loop_windows: eta {eta} must be 0 (a stochastic step would need per-window noise unfolded "
-                             "from one long draw)")
+            raise ValueError(f"{who}: eta {eta} must be 0 (a stochastic step would need per-window noise unfolded from one long draw)")
         if cond_fn is not None:
-            raise ValueError("ddim_sample_loop_windows: cond_fn is not supported (guided windowed loops are not built)")
+            raise ValueError(f"{who}: cond_fn is not supported (guided windowed loops are not built)")
+        w = self._windows_setup(who, model, shape, plan, window, overlap, lengths, noise, model_kwargs, skip_timesteps, init_image,
+                                denoised_fn, device)
+        x, plan, indices = w.x, w.plan, w.indices
+        # one native call, or with the x0-hat dump chunks bounded like the other loops' ([steps, N, F, 1, W] at once otherwise)
+        chunk = len(indices) if not dump_all_xstart else max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
+        it = range(0, len(indices), chunk)
+        if progress:
+            from tqdm.auto import tqdm
+            it = tqdm(it)
+        dumps = []
+        for c0 in it:
+            idx = indices[c0:c0 + chunk]
+            last = c0 + chunk >= len(indices)
+            res = w.eng.sample_loop_windows(w.sch, x, plan, idx[0], idx[-1], cfg=w.cfg is not None, scale=w.scale,
+                                            mask=w.mask if w.mask is not None else w.nmask, motion=w.motion, mask_noise=w.nmask is not None,
+                                            clip_denoised=clip_denoised, dump_xstart=bool(dump_all_xstart),
+                                            fold_out=w.out_long if last else None)
+            if dump_all_xstart:
+                self._fold_dumps(res[1], len(idx), w, dumps)
+        result = dumps if dump_all_xstart else w.out_long
+        return (result, x) if return_windows else result
+
+    def _windows_setup(self, who, model, shape, plan, window, overlap, lengths, noise, model_kwargs, skip_timesteps, init_image,
+                       denoised_fn, device):
+        """What every windowed loop does in front of its first step, and what it refuses (ValueError, by `who`): the plan, the long x_T
+        and q_sample, the unfolded inpainting pair, the per-clip y entries gathered per window, lengths and mask from the plan, the
+        engine prepared on the windows' conditioning.  -> a namespace: denoiser, cfg, plan, shape, x (the windows), indices, kw (the
+        windows' model_kwargs), eng, sch, mask, motion, nmask, scale, out_long (an empty [C,F,1,L] for the fold)."""
+        import types
+        from . import windows as _win
         if denoised_fn is not None:
-            raise ValueError("ddim_sample_loop_windows: denoised_fn is not supported (it would run between the step and the stitch)")
+            raise ValueError(f"{who}: denoised_fn is not supported (it would run between the step and the stitch)")
         denoiser, cfg, _ = _unwrap(model)
         if denoiser is None:
-            raise ValueError("ddim_sample_loop_windows: the model is not the native denoiser (no mst_engine): the windowed loop "
+            raise ValueError(f"{who}: the model is not the native denoiser (no mst_engine): the windowed loop "
                              "runs inside the library only")
         if denoiser.training:
-            raise ValueError("ddim_sample_loop_windows: the model is in training mode; call .eval()")
+            raise ValueError(f"{who}: the model is in training mode; call .eval()")
         if self.model_mean_type != ModelMeanType.START_X:
-            raise ValueError("ddim_sample_loop_windows: the native loop predicts x_start only")
+            raise ValueError(f"{who}: the native loop predicts x_start only")
         if shape is None:
             src = noise if noise is not None else init_image
             if src is None:
-                raise ValueError("ddim_sample_loop_windows: shape is None and neither noise nor init_image gives one")
+                raise ValueError(f"{who}: shape is None and neither noise nor init_image gives one")
             shape = tuple(src.shape)
         shape = tuple(int(v) for v in shape)
         if len(shape) != 4 or shape[2] != 1:
-            raise ValueError(f"ddim_sample_loop_windows: shape {shape} is not (C, F, 1, L)")
+            raise ValueError(f"{who}: shape {shape} is not (C, F, 1, L)")
         device = self._loop_device(model, device)
         y = dict(self._y(model_kwargs))
         if plan is None:
             if window is None or overlap is None:
-                raise ValueError("ddim_sample_loop_windows: pass a plan, or window and overlap")
+                raise ValueError(f"{who}: pass a plan, or window and overlap")
             if lengths is None:
                 lengths = y.get('lengths')
             if lengths is None:
                 lengths = [shape[3]] * shape[0]
             if int(window) > _eng.MAX_FRAMES:
-                raise ValueError(f"ddim_sample_loop_windows: window {int(window)} is above the engine's limit of {_eng.MAX_FRAMES} frames")
+                raise ValueError(f"{who}: window {int(window)} is above the engine's limit of {_eng.MAX_FRAMES} frames")
             plan = _win.WindowPlan(lengths, window, overlap, device, long_frames=shape[3])
         if plan.window > _eng.MAX_FRAMES:
-            raise ValueError(f"ddim_sample_loop_windows: window {plan.window} is above the engine's limit of {_eng.MAX_FRAMES} frames")
+            raise ValueError(f"{who}: window {plan.window} is above the engine's limit of {_eng.MAX_FRAMES} frames")
         if (plan.n_clips, plan.long_frames) != (shape[0], shape[3]):
-            raise ValueError(f"ddim_sample_loop_windows: the plan is for {plan.n_clips} clips of {plan.long_frames} frames, "
+            raise ValueError(f"{who}: the plan is for {plan.n_clips} clips of {plan.long_frames} frames, "
                              f"the shape {shape} is not")
         # x_T, and q_sample of the init image, ONCE on the long tensors (the inpainting variant's noise mask is the long mask)
         device, img, indices = self._loop_setup(model, shape, noise, device, skip_timesteps, init_image, None, model_kwargs)
@@ -735,12 +765,71 @@ class GaussianDiffusion:
         eng = denoiser.mst_engine(plan.n_windows * (2 if cfg is not None else 1), plan.window)
         denoiser.mst_prepare(eng, y, cfg is not None)
         mask, motion = self._inpaint_pair(kw)
-        nmask = self._noise_mask(kw)
-        scale = y['scale'] if cfg is not None else None
-        sch = self._schedule(x.device)
-        out_long = th.empty(shape, dtype=th.float32, device=x.device)
-        # one native call, or with the x0-hat dump chunks bounded like the other loops' ([steps, N, F, 1, W] at once otherwise)
-        chunk = len(indices) if not dump_all_xstart else max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
+        return types.SimpleNamespace(denoiser=denoiser, cfg=cfg, plan=plan, shape=shape, x=x, indices=indices, kw=kw, eng=eng,
+                                     sch=self._schedule(x.device), mask=mask, motion=motion, nmask=self._noise_mask(kw),
+                                     scale=y['scale'] if cfg is not None else None,
+                                     out_long=th.empty(shape, dtype=th.float32, device=x.device))
+
+    @staticmethod
+    def _fold_dumps(dump, n, w, dumps):
+        """The windows' x0-hat differ on shared frames: each step's dump is stitched into one long tensor."""
+        from . import windows as _win
+        for j in range(n):
+            lng = th.empty_like(w.out_long)
+            _win.stitch_(dump[j], w.plan, long_out=lng)
+            dumps.append(lng)
+
+    def sample_loop_windows(self, model, shape=None, *, sampler="ddim", eta=0.0, cond_fn=None, plan=None, window=None, overlap=None,
+                            lengths=None, noise=None, clip_denoised=True, model_kwargs=None, skip_timesteps=0, init_image=None,
+                            progress=False, dump_all_xstart=False, return_windows=False, denoised_fn=None, const_noise=False,
+                            device=None):
+        """p_sample_loop (sampler="ddpm") or ddim_sample_loop at any eta (sampler="ddim"), with or without a cond_fn, on long clips
+        [C,F,1,L]: `ddim_sample_loop_windows` (whose other arguments, set-up and return values these are) extended by the noise term
+        and the guide.  For sampler="ddim", eta == 0 and no cond_fn it is that loop, bit for bit.
+        Noise: drawn in LONG-clip coordinates and unfolded, so windows that share a long frame receive the same number for it;
+        x_{t-1} stays linear in (x_t, x0-hat, noise) and the windows agree on shared frames after every stitch.  Per native call
+        (chunks of at most `noise_chunk` steps and `noise_chunk_bytes`, as in the plain loops): noise_source == "philox":
+        windows.noise_windows(plan, F, seed + c0, 0, steps) with one seed a loop from torch's generator; otherwise one th.randn of
+        the long shape per step, unfolded.  Nothing is drawn for sampler="ddim" at eta == 0.
+        cond_fn: a guidance.TargetGuide takes LONG operands (target and mask broadcast to [C,F,1,L] and unfolded, weight gathered per
+        window) and the loop stays one native call per chunk; any other callable is evaluated on the folded long clip in front of
+        every step, with the caller's long model_kwargs, and its gradient is unfolded (one step per native call).  The x0-hat dump is
+        the unguided x0-hat.
+        Refused: what ddim_sample_loop_windows refuses of model, plan and denoised_fn, an unknown sampler (ValueError), const_noise
+        (NotImplementedError)."""
+        from . import windows as _win
+        from .guidance import TargetGuide
+        who = "sample_loop_windows"
+        if sampler not in ("ddim", "ddpm"):
+            raise ValueError(f"{who}: unknown sampler {sampler!r} ('ddim' or 'ddpm': PLMS and the reverse DDIM step over windows are not built)")
+        if const_noise:
+            raise NotImplementedError(f"{who}: const_noise is not built for windows")
+        w = self._windows_setup(who, model, shape, plan, window, overlap, lengths, noise, model_kwargs, skip_timesteps, init_image,
+                                denoised_fn, device)
+        x, plan, indices = w.x, w.plan, w.indices
+        smp = _eng.SAMPLER_DDPM if sampler == "ddpm" else _eng.SAMPLER_DDIM
+        noisy = sampler == "ddpm" or eta != 0.0                 # the step has a noise term: the loop reads a buffer
+        philox = self.noise_source == "philox"
+        guide = None
+        if isinstance(cond_fn, TargetGuide):
+            wt = cond_fn.weight
+            if wt.numel() not in (1, plan.n_clips):
+                raise ValueError(f"{who}: TargetGuide weight has {wt.numel()} values for {plan.n_clips} clips (one value, or one per clip)")
+            long_op = lambda v, what: _win.unfold(_eng._operand(v, w.shape, what, _eng.RULE_BROADCAST, x.device), plan)
+            guide = self._target_guide_args(TargetGuide(
+                long_op(cond_fn.target, "target"), None if cond_fn.mask is None else long_op(cond_fn.mask, "guide mask"),
+                wt if wt.numel() == 1 else wt[plan.win_clip_tensor().to(wt.device)], cond_fn.alphas_cumprod), x)
+        per_step = cond_fn is not None and guide is None
+        bound = max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
+        if per_step:
+            chunk = 1
+        elif noisy:
+            chunk = max(1, min(int(self.noise_chunk), bound))
+        else:
+            chunk = len(indices) if not dump_all_xstart else bound
+        seed = int(th.randint(0, 2 ** 31 - 1, (1,)).item()) if philox and noisy else 0
+        if w.cfg is not None:
+            w.eng.check_guidance_scale(w.scale)
         it = range(0, len(indices), chunk)
         if progress:
             from tqdm.auto import tqdm
@@ -749,17 +838,28 @@ class GaussianDiffusion:
         for c0 in it:
             idx = indices[c0:c0 + chunk]
             last = c0 + chunk >= len(indices)
-            res = eng.sample_loop_windows(sch, x, plan, idx[0], idx[-1], cfg=cfg is not None, scale=scale,
-                                          mask=mask if mask is not None else nmask, motion=motion, mask_noise=nmask is not None,
-                                          clip_denoised=clip_denoised, dump_xstart=bool(dump_all_xstart),
-                                          fold_out=out_long if last else None)
+            buf = None
+            if noisy and philox:
+                buf = _win.noise_windows(plan, w.shape[1], seed + c0, 0, len(idx))
+            elif noisy:
+                buf = th.stack([_win.unfold(th.randn_like(w.out_long), plan) for _ in idx])
+            if per_step:
+                _win.stitch_(x, plan, long_out=w.out_long)          # the windows agree on shared frames: a copy, x keeps its bits
+                t = th.full((plan.n_clips,), int(idx[0]), device=x.device, dtype=th.long)
+                grad = self._cond_gradient(cond_fn, w.out_long, t, model_kwargs)
+                guide = _eng.guide_args(x, grad=_win.unfold(grad.to(device=x.device).contiguous(), plan))
+            res = w.eng.window_sample_loop(w.sch, x, plan, idx[0], idx[-1], smp, eta, cfg=w.cfg is not None, scale=w.scale,
+                                           mask=w.mask if w.mask is not None else w.nmask, motion=w.motion,
+                                           mask_noise=w.nmask is not None, clip_denoised=clip_denoised, noise=buf, guide=guide,
+                                           dump_xstart=bool(dump_all_xstart), fold_out=w.out_long if last else None)
             if dump_all_xstart:
-                for j in range(len(idx)):      # the windows' x0-hat differ on shared frames: each step's dump is stitched into one long tensor
-                    lng = th.empty_like(out_long)
-                    _win.stitch_(res[1][j], plan, long_out=lng)
-                    dumps.append(lng)
-        result = dumps if dump_all_xstart else out_long
+                self._fold_dumps(res[1], len(idx), w, dumps)
+        result = dumps if dump_all_xstart else w.out_long
         return (result, x) if return_windows else result
+
+    def p_sample_loop_windows(self, model, shape=None, **kwargs):
+        """p_sample_loop on long clips: `sample_loop_windows(sampler="ddpm")`."""
+        return self.sample_loop_windows(model, shape, sampler="ddpm", **kwargs)
 
     # -- DDIM inversion and its decode half.  The reference has the step (ddim_reverse_sample) and no loop around it: these entries
     #    are additions (INTEGRATION.md).

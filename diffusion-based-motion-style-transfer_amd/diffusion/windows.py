@@ -5,7 +5,9 @@ feature rows are frame-local (the root enters as velocities, everything else is 
 clip are the rows of the sub-clip: a long clip [C,F,1,L] is cut into windows [N,F,1,W] of the model's own length, all windows of all
 clips are sampled as one batch, and after every step the frames two or more windows share are replaced, in all of them, by one
 weighted mean (MultiDiffusion / DoubleTake-style synchronisation).  The arithmetic is csrc/mst_window.h; this is the plan and the
-plumbing.  `GaussianDiffusion.ddim_sample_loop_windows` is the loop.
+plumbing.  `GaussianDiffusion.ddim_sample_loop_windows` is the deterministic loop, `sample_loop_windows` / `p_sample_loop_windows` the
+general one: ancestral, stochastic DDIM and guided.  Their noise is drawn in long-clip coordinates (`noise_windows`), so windows that
+share a long frame receive the same number for it and the stitch stays exact bookkeeping.
 
 The plan rule (`plan_windows`), stride S = W - O:
   len <= W    one window at start 0; its frames >= len are zero padding, as the demo pads;
@@ -134,3 +136,12 @@ def fold(windows, plan):
     long = torch.empty((plan.n_clips, windows.shape[1], 1, plan.long_frames), dtype=torch.float32, device=plan.device)
     stitch_(windows.clone(), plan, long_out=long)
     return long
+
+
+def noise_windows(plan, feats, seed, step0, nsteps):
+    """The noise of `nsteps` stochastic steps, drawn in long-clip coordinates (mst_window_noise) -> [nsteps, N, F, 1, W], the buffer a
+    windowed loop reads.  Entry j is unfold(Z_j), Z_j [C,F,1,L] = the engine's philox_normal(C, L, seed, step0 + j): every window that
+    covers a long frame holds the same bits for it; window frames at or past a clip's length are 0.0."""
+    out = torch.empty((int(nsteps), plan.n_windows, int(feats), 1, plan.window), dtype=torch.float32, device=plan.device)
+    N.check(N.lib().mst_window_noise(plan.handle, int(feats), int(seed), int(step0), int(nsteps), N.ptr(out), N.stream_ptr(plan.device)))
+    return out

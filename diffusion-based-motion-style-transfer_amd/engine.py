@@ -662,6 +662,59 @@ class DenoiserEngine:
         self._loop_keepalive = keep
         return (x, dump) if dump_xstart else x
 
+    def window_sample_loop(self, schedule, x, plan, t_start, t_end=0, sampler=SAMPLER_DDPM, eta=0.0, cfg=False, scale=None, mask=None,
+                           motion=None, mask_noise=True, clip_denoised=False, noise=None, guide=None, dump_xstart=False, fold_out=None):
+        """SAMPLER_DDPM, or SAMPLER_DDIM at any eta, over the windows `x` ([N,F,1,W], in place) of a `windows.WindowPlan`, stitched
+        behind every step (mst_window_sample_loop): equal, bit for bit, to one-step `sample_loop` calls with `windows.stitch_` between
+        them.  noise: [nsteps,N,F,1,W] from `windows.noise_windows` (or any buffer whose windows agree on shared frames), required where
+        the step has a noise term (SAMPLER_DDPM, or eta != 0): the in-kernel draw is keyed by window and is refused there.
+        guide: a `guide_args(...)` pair on the windows' operands.  fold_out: a [C,F,1,L] float32 tensor the last stitch also writes the
+        long clips into (None: no fold).  Returns x (and the [nsteps,N,F,1,W] x0-hat dump of the windows -- with a guide the unguided
+        x0-hat -- as the steps wrote it, when requested)."""
+        assert _need_gpu(x, "x").dtype == torch.float32 and x.is_contiguous()
+        if cfg:
+            self.check_guidance_scale(scale)
+        B, F, one, T = x.shape
+        nsteps = abs(t_start - t_end) + 1
+        a = N.MstLoopArgs()
+        a.batch, a.frames, a.cfg, a.sampler = B, T, int(bool(cfg)), int(sampler)
+        a.mask_noise, a.clip_denoised = int(bool(mask_noise)), int(bool(clip_denoised))
+        a.t_start, a.t_end, a.eta = int(t_start), int(t_end), float(eta)
+        keep = []
+        if noise is not None:
+            assert noise.numel() == nsteps * x.numel(), (noise.shape, nsteps, x.shape)
+            single = nsteps == 1 and isinstance(noise, torch.Tensor) and noise.dim() == x.dim()
+            noise = _operand(noise, tuple(x.shape) if single else (nsteps,) + tuple(x.shape), "noise", RULE_EQUAL, self.device)
+            a.noise_mode, a.noise_dev = NOISE_BUFFER, noise.data_ptr()
+            keep.append(noise)
+        else:
+            a.noise_mode, a.seed = NOISE_PHILOX, 0              # taken only where sigma is 0 (DDIM at eta 0): the draw is multiplied away
+        mask, motion = _mask_pair(mask, motion, x.shape, self.device)
+        scale = None if scale is None else _operand(scale, (B,), "scale", RULE_SCALE, self.device)
+        for name, val in (("scale_dev", scale), ("inpainting_mask_dev", mask), ("inpainted_motion_dev", motion)):
+            if val is not None:
+                keep.append(val)
+                setattr(a, name, val.data_ptr())
+        a.x_dev = x.data_ptr()
+        dump = None
+        if dump_xstart:
+            dump = torch.empty((nsteps,) + tuple(x.shape), dtype=torch.float32, device=self.device)
+            a.xstart_dump_dev = dump.data_ptr()
+        if fold_out is not None:
+            want = (plan.n_clips, F, one, plan.long_frames)
+            assert fold_out.is_cuda and fold_out.dtype == torch.float32 and fold_out.is_contiguous() and tuple(fold_out.shape) == want, \
+                f"fold_out: a contiguous float32 {want} tensor"
+        if guide is not None:
+            keep.append(guide[1])
+        N.check(N.lib().mst_window_plan_set_fold(plan.handle, N.ptr(fold_out)))
+        try:
+            N.check(N.lib().mst_window_sample_loop(self.handle, schedule.handle, C.byref(a), plan.handle,
+                                                   C.byref(guide[0]) if guide is not None else None, N.stream_ptr(self.device)))
+        finally:
+            N.check(N.lib().mst_window_plan_set_fold(plan.handle, None))
+        self._loop_keepalive = keep
+        return (x, dump) if dump_xstart else x
+
     def sample_loop_plms(self, schedule, x, t_start, t_end=0, order=2, steps_done=0, hist=None, cfg=False, scale=None, mask=None,
                          motion=None, clip_denoised=False, dump_xstart=False, noise=None, seed=None, eta=0.0, mask_noise=False):
         """Run PLMS chain steps at indices t_start..t_end (descending) in place on `x`.  hist: the [3,B,F,1,T] float32 eps ring (chain

@@ -261,7 +261,24 @@ int mst_sample_loop_guided(mst_engine* e, const mst_schedule* s, const mst_loop_
  *                       Refused, each by name: any sampler but MST_SAMPLER_DDIM; eta != 0 (for the deterministic step x_{t-1} is linear
  *                       in x_t and x0-hat, so windows that start from one long x_T hold identical values on shared frames after every
  *                       stitch, and the mean is a mean over x0-hat alone); batch != the plan's windows; frames != the plan's window; a
- *                       plan on another device.  It takes no guide: guided windowed loops are not built.
+ *                       plan on another device.  It takes no guide: mst_window_sample_loop does.
+ *   mst_window_noise    extends mst_philox_normal to windows: out_dev [nsteps,N,F,1,W], the layout an MST_NOISE_BUFFER loop reads (step
+ *                       j at j * N*F*W).  Entry j = unfold(Z_j), Z_j [C,F,1,L] = mst_philox_normal(C, F, L, seed, step0 + j): element
+ *                       (c, f, l) is component l & 3 of the four normals of counter (l >> 2, f, c, step0 + j) under `seed` -- the noise
+ *                       is drawn in LONG-clip coordinates, so every window that covers a long frame receives the same bits for it
+ *                       (the in-kernel draw is keyed by the window, and the stitch's mean would shrink the variance on shared frames).
+ *                       Every element is written; window frames at or past the clip's length get 0.0.  One draw per long quad, no
+ *                       atomics.  Refused, each by name: a null plan, a null out, feats < 1, nsteps < 1, more elements than one launch
+ *                       takes.
+ *   mst_window_sample_loop   extends mst_sample_loop_windows by the noise term and by mst_sample_loop_guided's guide (g may be NULL):
+ *                       MST_SAMPLER_DDPM, or MST_SAMPLER_DDIM at any eta.  With noise drawn by mst_window_noise x_{t-1} stays linear
+ *                       in (x_t, x0-hat, noise), so the windows still agree on shared frames after every stitch.  The same launch
+ *                       sequence as mst_sample_loop_windows (host-enqueued steps, join, stitch, fork), so an n-step call equals n
+ *                       one-step mst_sample_loop / mst_sample_loop_guided calls with mst_window_stitch between them, bit for bit.
+ *                       Refused, each by name: any other sampler (PLMS and MST_SAMPLER_DDIM_REVERSE over windows are not built);
+ *                       MST_NOISE_PHILOX where the step has a noise term (MST_SAMPLER_DDPM, or eta != 0), and a missing noise buffer
+ *                       there; batch != the plan's windows; frames != the plan's window; a plan on another device; what
+ *                       mst_sample_loop_guided refuses of a guide (MST_GUIDE_GRADIENT: t_start == t_end).
  * ----------------------------------------------------------------------------------------- */
 typedef struct mst_window_plan mst_window_plan;
 int  mst_window_max_frames(void);
@@ -272,6 +289,9 @@ int  mst_window_plan_set_fold(mst_window_plan* p, float* long_out_dev);
 int  mst_window_unfold(const mst_window_plan* p, const float* long_dev, int32_t feats, float* win_dev, void* stream);
 int  mst_window_stitch(const mst_window_plan* p, float* win_dev, int32_t feats, float* long_out_dev, void* stream);
 int  mst_sample_loop_windows(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_window_plan* p, void* stream);
+int  mst_window_noise(const mst_window_plan* p, int32_t feats, uint64_t seed, uint32_t step0, int32_t nsteps, float* out_dev, void* stream);
+int  mst_window_sample_loop(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_window_plan* p,
+                            const mst_guide_args* g /* may be NULL */, void* stream);
 
 /* Number of independent clip slices (1..3) mst_sample_loop runs on separate streams for this
  * batch of `frames`-frame clips (frames <= 0: the engine's max_frames; the policy depends on the

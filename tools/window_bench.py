@@ -8,9 +8,14 @@ same box, interleaved:
   (c) independent, MST_FUSE_FRAMES=0 -- the same on an engine created with MST_FUSE_FRAMES=0: (a)'s launch sequence without the stitch
                         and the per-step join.  (a) - (c) is the feature's cost.
 
+  (d) stochastic windows (only with --sampler ddpm, or --sampler ddim --eta != 0) -- mst_window_sample_loop reading buffer noise that
+                        mst_window_noise drew in long-clip coordinates, in chunks bounded as GaussianDiffusion bounds them (64 steps,
+                        256 MB); the fill is inside the timed region.  (d) - (a) is what the noise term costs over the deterministic
+                        windowed loop of the same run: the fill, and the step's 4 bytes per element of buffer read.
+
 (b) and (c) run the unchanged entry point.  One untimed warm-up loop each, then `--reps` loops each, alternating, timed with device
 events around a synchronised call; medians.  Also: k_window_unfold and k_window_stitch (with the fold) alone, event-timed over `--kernel-reps`
-launches.  Prints one JSON line."""
+launches; with (d) also k_window_noise alone, per step.  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -30,13 +35,15 @@ def main():
     ap.add_argument("--window", type=int, default=196)
     ap.add_argument("--overlap", type=int, default=48)
     ap.add_argument("--kernel-reps", type=int, default=50)
+    ap.add_argument("--sampler", choices=("ddim", "ddpm"), default="ddim", help="ddpm, or ddim with --eta != 0: also time leg (d)")
+    ap.add_argument("--eta", type=float, default=0.0)
     args = ap.parse_args()
     import numpy as np
     import torch
     import mst_amd  # noqa: F401
     from mst_amd import synthetic as syn
-    from mst_amd.diffusion.windows import WindowPlan, stitch_, unfold
-    from mst_amd.engine import DenoiserEngine, Schedule, SAMPLER_DDIM
+    from mst_amd.diffusion.windows import WindowPlan, noise_windows, stitch_, unfold
+    from mst_amd.engine import DenoiserEngine, Schedule, SAMPLER_DDIM, SAMPLER_DDPM
     from oracle import schedule
 
     dev = torch.device("cuda:0")
@@ -90,6 +97,18 @@ def main():
         "independent_fuse_frames_0": lambda: eng_plain.sample_loop(sch, x0.clone(), n - 1, 0, SAMPLER_DDIM, eta=0.0, mask=mask, motion=motion,
                                                                    seed=0),
     }
+    noisy = args.sampler == "ddpm" or args.eta != 0.0
+    chunk = max(1, min(64, (256 << 20) // (x0.numel() * 4)))       # GaussianDiffusion.noise_chunk / noise_chunk_bytes
+
+    def stochastic():
+        x = x0.clone()
+        for c0 in range(0, n, chunk):
+            k = min(chunk, n - c0)
+            buf = noise_windows(plan, F, 1 + c0, 0, k)
+            eng.window_sample_loop(sch, x, plan, n - 1 - c0, n - c0 - k, SAMPLER_DDPM if args.sampler == "ddpm" else SAMPLER_DDIM, args.eta,
+                                   mask=mask, motion=motion, noise=buf, fold_out=out_long if c0 + k == n else None)
+    if noisy:
+        legs["windows_stochastic"] = stochastic
     for fn in legs.values():
         fn()
     ms = {k: [] for k in legs}
@@ -106,6 +125,15 @@ def main():
     del scratch
     k_un = timed(lambda: [unfold(x_long, plan) for _ in range(args.kernel_reps)]) / args.kernel_reps
     cost = med["windows"] - med["independent_fuse_frames_0"]
+    extra = {}
+    if noisy:
+        def fills():
+            for _ in range(args.kernel_reps):                       # (each buffer is dropped at once: the allocator hands the same block out again)
+                noise_windows(plan, F, 1, 0, chunk)
+        k_nz = timed(fills) / args.kernel_reps / chunk
+        d = med["windows_stochastic"] - med["windows"]
+        extra = {"sampler": args.sampler, "eta": args.eta, "noise_chunk_steps": chunk, "noise_fill_us_per_step": round(k_nz * 1e3, 2),
+                 "noise_term_cost_ms_per_step": round(d / n, 4), "noise_term_cost_over_windows": round(d / med["windows"], 4)}
     print(json.dumps({
         "long_shape": list(shp), "window": W, "overlap": O, "windows": N, "slices": eng.loop_slices(N, False, W), "steps": n, "reps": args.reps,
         **{f"{k}_ms": round(v, 2) for k, v in med.items()}, **{f"{k}_all_ms": [round(t, 2) for t in v] for k, v in ms.items()},
@@ -113,7 +141,7 @@ def main():
         "feature_cost_ms_per_step": round(cost / n, 4), "feature_cost_over_fuse_frames_0": round(cost / med["independent_fuse_frames_0"], 4),
         "windows_over_independent": round(med["windows"] / med["independent"], 4),
         "long_frames_per_s": round(C * L / med["windows"] * 1e3, 1),
-        "stitch_fold_us": round(k_st * 1e3, 2), "unfold_us": round(k_un * 1e3, 2), "windows_mb": round(xs.numel() * 4 / 1e6, 1)}))
+        "stitch_fold_us": round(k_st * 1e3, 2), "unfold_us": round(k_un * 1e3, 2), "windows_mb": round(xs.numel() * 4 / 1e6, 1), **extra}))
 
 
 if __name__ == "__main__":
