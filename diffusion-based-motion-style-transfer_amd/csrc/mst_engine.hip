@@ -32,6 +32,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_feet.h"
 #include "mst_ik.h"
 #include "mst_encode.h"
+#include "mst_bvh.h"
 #include "mst_window.h"
 #include "mst_plan.h"
 
@@ -3380,6 +3381,27 @@ extern "C" int mst_encode_max_frames(int32_t joints, int32_t mode) {
     }
     return kEncMaxFrames;
 }
+// The kinematic chains, link by link in the reference's order (common/skeleton.py:88-103), into the tables k_encode and k_retarget walk.
+static int enc_fill_links(const char* who, EncArgs& p, int joints, const int32_t* chains, const int32_t* chain_starts, int num_chains) {
+    bool placed[kEncMaxJoints] = {true};
+    for (int c = 0; c < num_chains; c++) {
+        const int lo = chain_starts[c], hi = chain_starts[c + 1];
+        if (lo < 0 || hi <= lo) return fail("%s: chain %d is empty", who, c);
+        for (int k = lo; k < hi; k++)
+            if (chains[k] < 0 || chains[k] >= joints) return fail("%s: joint %d of chain %d outside 0..%d", who, chains[k], c, joints - 1);
+        if (!placed[chains[lo]]) return fail("%s: chain %d starts at joint %d, which no earlier chain has placed", who, c, chains[lo]);
+        for (int k = lo + 1; k < hi; k++) {
+            if (placed[chains[k]]) return fail("%s: joint %d is named twice as a child (chain %d)", who, chains[k], c);
+            placed[chains[k]] = true;
+            p.link_child[p.n_links] = chains[k];
+            p.link_parent[p.n_links] = chains[k - 1];
+            p.link_first[p.n_links] = k == lo + 1;
+            p.named[chains[k]] = 1;
+            p.n_links++;
+        }
+    }
+    return 0;
+}
 extern "C" int mst_encode_motion(const float* positions, const float* rotations, const int32_t* lengths, const float* mean, const float* stdv,
                                  int32_t batch, int32_t frames, int32_t joints, int32_t mode, const int32_t* face_ids,
                                  const int32_t* foot_ids, const int32_t* chains, const int32_t* chain_starts, int32_t num_chains,
@@ -3408,25 +3430,7 @@ extern "C" int mst_encode_motion(const float* positions, const float* rotations,
             if (foot_ids[i] < 0 || foot_ids[i] >= joints) return fail("mst_encode_motion: foot joint %d outside 0..%d", foot_ids[i], joints - 1);
             p.fid[i] = foot_ids[i];
         }
-    if (chains && chain_starts && num_chains > 0) {
-        bool placed[kEncMaxJoints] = {true};
-        for (int c = 0; c < num_chains; c++) {
-            const int lo = chain_starts[c], hi = chain_starts[c + 1];
-            if (lo < 0 || hi <= lo) return fail("mst_encode_motion: chain %d is empty", c);
-            for (int k = lo; k < hi; k++)
-                if (chains[k] < 0 || chains[k] >= joints) return fail("mst_encode_motion: joint %d of chain %d outside 0..%d", chains[k], c, joints - 1);
-            if (!placed[chains[lo]]) return fail("mst_encode_motion: chain %d starts at joint %d, which no earlier chain has placed", c, chains[lo]);
-            for (int k = lo + 1; k < hi; k++) {
-                if (placed[chains[k]]) return fail("mst_encode_motion: joint %d is named twice as a child (chain %d)", chains[k], c);
-                placed[chains[k]] = true;
-                p.link_child[p.n_links] = chains[k];
-                p.link_parent[p.n_links] = chains[k - 1];
-                p.link_first[p.n_links] = k == lo + 1;
-                p.named[chains[k]] = 1;
-                p.n_links++;
-            }
-        }
-    }
+    if (chains && chain_starts && num_chains > 0) CHECK(enc_fill_links("mst_encode_motion", p, joints, chains, chain_starts, num_chains));
     if (raw_offsets)
         for (int j = 0; j < joints; j++)
             for (int k = 0; k < 3; k++) p.raw[j][k] = raw_offsets[3 * j + k];
@@ -3454,6 +3458,169 @@ extern "C" int mst_encode_motion(const float* positions, const float* rotations,
     p.local = local_positions;
     p.lvel = l_velocity;
     hipLaunchKernelGGL(k_encode, dim3(batch), dim3(kEncThreads), sizeof(float) * 6 * frames, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// Motion files (mst_bvh.h).  The decode keeps one scan bit a joint and wave in LDS and everything a frame needs in the caller's workspace,
+// so neither bound depends on the device: the joint cap is what the kernel arguments and the lane's two 64-bit scan registers hold, the
+// frame cap what one workgroup should walk (see the constants).
+extern "C" int mst_bvh_max_joints(void) { return kBvhMaxJoints; }
+extern "C" int mst_bvh_max_frames(int32_t joints) {
+    if (joints < 1 || joints > kBvhMaxJoints) {
+        fail("mst_bvh_max_frames: joints %d outside 1..%d (mst_bvh_max_joints)", joints, kBvhMaxJoints);
+        return -1;
+    }
+    return kBvhMaxFrames;
+}
+extern "C" int mst_bvh_decode(const float* channels, const int32_t* lengths, int32_t batch, int32_t frames, int32_t num_channels,
+                              int32_t joints, const int32_t* parents, const int32_t* rot_cols, const int32_t* pos_cols, const float* offsets,
+                              const int32_t* order, float scale, int32_t stride, int32_t phase, const int32_t* select, int32_t num_select,
+                              float* workspace, float* rotations, float* positions, float* local_positions, float* global_rotations,
+                              void* stream) {
+    if (joints < 1 || joints > kBvhMaxJoints) return fail("mst_bvh_decode: joints %d outside 1..%d (mst_bvh_max_joints)", joints, kBvhMaxJoints);
+    if (batch < 1) return fail("mst_bvh_decode: batch %d < 1", batch);
+    if (frames < 1) return fail("mst_bvh_decode: frames %d < 1", frames);
+    if (frames > kBvhMaxFrames) return fail("mst_bvh_decode: frames %d > %d (mst_bvh_max_frames)", frames, kBvhMaxFrames);
+    if (num_channels < 3 || num_channels > 6 * joints) return fail("mst_bvh_decode: %d channels outside 3..6 * %d", num_channels, joints);
+    if (stride < 1) return fail("mst_bvh_decode: stride %d < 1", stride);
+    if (phase < 0 || phase >= stride) return fail("mst_bvh_decode: phase %d outside 0..%d", phase, stride - 1);
+    if (phase >= frames) return fail("mst_bvh_decode: phase %d leaves no frame of %d", phase, frames);
+    if (num_select < 0 || num_select > kBvhMaxSel) return fail("mst_bvh_decode: %d selected joints outside 0..%d", num_select, kBvhMaxSel);
+    if (!channels || !parents || !rot_cols || !pos_cols || !offsets || !order || !workspace || !rotations || !positions || (num_select && !select))
+        return fail("mst_bvh_decode: null argument");
+    if (!(order[0] >= 0 && order[0] <= 2 && order[1] >= 0 && order[1] <= 2 && order[2] >= 0 && order[2] <= 2) || order[0] == order[1] ||
+        order[1] == order[2] || order[0] == order[2])
+        return fail("mst_bvh_decode: rotation order (%d, %d, %d) is no permutation of the axes 0, 1, 2", order[0], order[1], order[2]);
+    BvhArgs p{};
+    if (parents[0] != -1) return fail("mst_bvh_decode: parents[0] = %d: joint 0 is the root (-1)", parents[0]);
+    for (int j = 0; j < joints; j++) {
+        if (j && (parents[j] < 0 || parents[j] >= j))
+            return fail("mst_bvh_decode: parents[%d] = %d: not a tree rooted at 0 with parents[j] < j", j, parents[j]);
+        if (rot_cols[j] < -1 || rot_cols[j] + 3 > num_channels) return fail("mst_bvh_decode: rotation column %d of joint %d outside the %d channels", rot_cols[j], j, num_channels);
+        if (pos_cols[j] < -1 || pos_cols[j] + 3 > num_channels) return fail("mst_bvh_decode: position column %d of joint %d outside the %d channels", pos_cols[j], j, num_channels);
+        p.parent[j] = (short)parents[j];
+        p.rot_col[j] = (short)rot_cols[j];
+        p.pos_col[j] = (short)pos_cols[j];
+        for (int k = 0; k < 3; k++) p.off[j][k] = offsets[3 * j + k];
+    }
+    for (int s = 0; s < num_select; s++) {
+        const int j = select[s];
+        if (j < 0 || j >= joints) return fail("mst_bvh_decode: selected joint %d outside 0..%d", j, joints - 1);
+        for (int q = 0; q < s; q++)
+            if (select[q] == j) return fail("mst_bvh_decode: joint %d is selected twice", j);
+        int anc = parents[j];
+        while (anc >= 0) {                   // the nearest selected ancestor
+            bool in = false;
+            for (int q = 0; q < num_select; q++) in = in || select[q] == anc;
+            if (in) break;
+            anc = parents[anc];
+        }
+        p.sel[s] = (short)j;
+        p.sel_anc[s] = (short)anc;
+        p.sel_direct[s] = anc == parents[j];            // the file parent itself, or the file's root (both -1)
+    }
+    p.ch = channels;
+    p.lengths = lengths;
+    p.B = batch;
+    p.T = frames;
+    p.C = num_channels;
+    p.Jf = joints;
+    p.nsel = num_select;
+    p.stride = stride;
+    p.phase = phase;
+    p.Tout = (frames - phase + stride - 1) / stride;
+    p.scale = scale;
+    for (int k = 0; k < 3; k++) p.axis[k] = order[k];
+    p.ws = workspace;
+    p.rot = rotations;
+    p.pos = positions;
+    p.lpos = local_positions;
+    p.grot = global_rotations;
+    hipLaunchKernelGGL(k_bvh_decode, dim3(batch), dim3(kBvhThreads), 0, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_quats_to_channels(const float* quats, const float* root_pos, const float* positions, const int32_t* perm, int32_t batch,
+                                     int32_t frames, int32_t joints, int32_t order, float* out, void* stream) {
+    if (joints < 1 || joints > kBvhMaxJoints) return fail("mst_quats_to_channels: joints %d outside 1..%d (mst_bvh_max_joints)", joints, kBvhMaxJoints);
+    if (batch < 1 || frames < 1) return fail("mst_quats_to_channels: %d clips of %d frames", batch, frames);
+    if (order != kQ2cZyx && order != kQ2cXzy)
+        return fail("mst_quats_to_channels: order %d is neither 0 ('zyx') nor 1 ('xzy'), the file orders whose reverse q2eul converts", order);
+    if (!quats || !root_pos || !perm || !out) return fail("mst_quats_to_channels: null argument");
+    Q2cArgs p{};
+    bool seen[kBvhMaxJoints] = {};
+    for (int s = 0; s < joints; s++) {
+        if (perm[s] < 0 || perm[s] >= joints || seen[perm[s]]) return fail("mst_quats_to_channels: perm[%d] = %d: not a permutation of 0..%d", s, perm[s], joints - 1);
+        seen[perm[s]] = true;
+        p.perm[s] = (short)perm[s];
+    }
+    if (perm[0] != 0) return fail("mst_quats_to_channels: perm[0] = %d: the root is written first", perm[0]);
+    p.quats = quats;
+    p.root_pos = root_pos;
+    p.positions = positions;
+    p.B = batch;
+    p.T = frames;
+    p.J = joints;
+    p.order = order;
+    p.out = out;
+    const long long n = (long long)batch * frames * joints;
+    hipLaunchKernelGGL(k_quats_to_channels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_retarget_max_frames(int32_t joints) {
+    if (joints < 2 || joints > kEncMaxJoints) {
+        fail("mst_retarget_max_frames: joints %d outside 2..%d", joints, kEncMaxJoints);
+        return -1;
+    }
+    return kRetMaxFrames;
+}
+extern "C" int mst_retarget_joints(const float* positions, const int32_t* lengths, int32_t batch, int32_t frames, int32_t joints,
+                                   const int32_t* face_ids, const int32_t* chains, const int32_t* chain_starts, int32_t num_chains,
+                                   const float* raw_offsets, const float* target_offsets, const int32_t* leg_ids, float* out, void* stream) {
+    if (joints < 2 || joints > kEncMaxJoints) return fail("mst_retarget_joints: joints %d outside 2..%d", joints, kEncMaxJoints);
+    if (batch < 1) return fail("mst_retarget_joints: batch %d < 1", batch);
+    if (frames < 1) return fail("mst_retarget_joints: frames %d < 1", frames);
+    if (frames > kRetMaxFrames) return fail("mst_retarget_joints: frames %d > %d (mst_retarget_max_frames)", frames, kRetMaxFrames);
+    if (!positions || !face_ids || !chains || !chain_starts || num_chains < 1 || !raw_offsets || !target_offsets || !leg_ids || !out)
+        return fail("mst_retarget_joints: null argument");
+    if (out == positions) return fail("mst_retarget_joints: the output may not be the input");
+    EncArgs p{};
+    RetArgs x{};
+    for (int i = 0; i < 4; i++) {
+        if (face_ids[i] < 0 || face_ids[i] >= joints) return fail("mst_retarget_joints: face joint %d outside 0..%d", face_ids[i], joints - 1);
+        for (int j = 0; j < i; j++)
+            if (face_ids[i] == face_ids[j]) return fail("mst_retarget_joints: duplicate face joint %d", face_ids[i]);
+        p.face[i] = face_ids[i];
+    }
+    CHECK(enc_fill_links("mst_retarget_joints", p, joints, chains, chain_starts, num_chains));
+    for (int a = 0; a < 2; a++) {
+        if (leg_ids[a] < 1 || leg_ids[a] >= joints) return fail("mst_retarget_joints: leg joint %d outside 1..%d", leg_ids[a], joints - 1);
+        x.leg[a] = leg_ids[a];
+        x.leg_parent[a] = 0;                 // common/skeleton.py:11-15: a joint no chain names hangs off the root
+        for (int l = 0; l < p.n_links; l++)
+            if (p.link_child[l] == leg_ids[a]) x.leg_parent[a] = p.link_parent[l];
+    }
+    for (int j = 0; j < joints; j++)
+        for (int k = 0; k < 3; k++) {
+            p.raw[j][k] = raw_offsets[3 * j + k];
+            x.tgt[j][k] = target_offsets[3 * j + k];
+        }
+    for (int a = 0; a < 2; a++) {
+        float m = 0.f;
+        for (int k = 0; k < 3; k++) m = fmaxf(m, fabsf(x.tgt[x.leg[a]][k]));
+        x.tgt_leg += m;
+    }
+    p.pos = positions;
+    p.lengths = lengths;
+    p.B = batch;
+    p.T = frames;
+    p.J = joints;
+    x.out = out;
+    hipLaunchKernelGGL(k_retarget, dim3(batch), dim3(kEncThreads), 0, (hipStream_t)stream, p, x);
     HIPCHECK(hipGetLastError());
     return 0;
 }

@@ -9,9 +9,10 @@ The reference's gradient on the first three 6D components of every joint is not 
 in the storage autograd saved as x_raw, so the backward of x_raw / |x_raw| reads the joint's offset (for the root: the frame's r_pos) in
 x_raw's place.  Its results are what parity means here, so that is the default; `true_gradient=True` gives the true gradient.
 
-Left out: `use_lbfgs` (no caller), `iter_num=None` (the reference's `while loss > 2e-5` never updates `loss` and never ends), BVH text
-writing (the reference's `Anim` / `save_bvh` are used when a checkout is importable), and `rotm2axangle`'s SVD branch for a rotation whose
-angle is an exact multiple of pi (common/rotation.py:467-472): such a joint gets the plain formula's result."""
+Left out: `use_lbfgs` (no caller), `iter_num=None` (the reference's `while loss > 2e-5` never updates `loss` and never ends), and
+`rotm2axangle`'s SVD branch for a rotation whose angle is an exact multiple of pi (common/rotation.py:467-472): such a joint gets the plain
+formula's result.  The BVH text is written by `utils/bvh.py`: `fit_joints_bvh(..., save=bvh.save_fit)` for one clip, `bvh.save_fits` for a
+`JointFit` batch; `fit_joints_bvh`'s default `save` is still the reference's `Anim` / `save_bvh`, imported from a checkout on the path."""
 import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
@@ -202,8 +203,8 @@ def _default_save():
         from data_loaders.humanml.common.bvh_utils import Anim, save_bvh  # noqa: F401
     except ImportError as e:
         raise ImportError("fit_joints_bvh: `Anim` and `save_bvh` of data_loaders.humanml.common.bvh_utils cannot be imported (no reference "
-                          "checkout on the path?); BVH writing is not reimplemented here -- pass save=callable(path, joint_quats, positions, "
-                          "real_offset, parents, names, frametime)") from e
+                          "checkout on the path?) -- pass save=mst_amd.utils.bvh.save_fit, which writes the file itself, or any "
+                          "save=callable(path, joint_quats, positions, real_offset, parents, names, frametime)") from e
     return _reference_save
 
 

@@ -223,3 +223,78 @@ def process_file(positions, face_joint_indx, fid_l, fid_r, feet_thre, n_raw_offs
     -> (data [T-1, 12J-1], global_positions [T, J, 3], positions [T, J, 3], l_velocity [T-1, 2]).  A zero-length bone in the raw offsets
     or the clip gives NaN in that joint's rotation columns, as in the reference."""
     return _process("process_file", positions, None, face_joint_indx, fid_l, fid_r, feet_thre, n_raw_offsets, kinematic_chain)
+
+
+# ------------------------------------------------------------------------------------------ one skeleton for every clip
+# Counterpart of `uniform_skeleton_basic` (data_loaders/humanml/scripts/motion_process.py:12-35; `uniform_skeleton` with its globals made
+# arguments): one native launch for a batch, one workgroup per clip (k_retarget, csrc/mst_bvh.h).
+def retarget_max_frames(joints):
+    """Longest clip `retarget_joints` takes (mst_retarget_max_frames)."""
+    n = int(N.lib().mst_retarget_max_frames(int(joints)))
+    if n < 0:
+        N.check(1)
+    return n
+
+
+def retarget_joints(positions, target_offset, raw_offsets, chains, l_idx, face_joint_indx, lengths=None):
+    """Joint positions [B, T, J, 3] moved onto the skeleton with bone offsets `target_offset` [J, 3] -> [B, T, J, 3].  Per clip: the source
+    offsets are frame 0's bone lengths along `raw_offsets` [J, 3]; the root is scaled by the ratio of leg lengths, each the sum over the two
+    joints `l_idx` of the offset's largest absolute component (the reference's measure, not a norm); the chain IK (smooth_forward=False,
+    frame 0's root quaternion the identity, every chain restarting from the root quaternion) gives the rotations and the forward kinematics
+    with the target offsets the result.  lengths [B]: 1 <= len <= T; frames past a clip are exact zeros.  A joint no chain names comes
+    back as zeros and a zero-length bone gives NaN, both as in the reference.  The input is not modified; one launch on the caller's
+    current stream."""
+    what = "retarget_joints"
+    if not torch.is_tensor(positions):
+        raise TypeError(f"{what}: positions is a tensor (uniform_skeleton_basic takes the reference's numpy clip)")
+    if positions.dim() != 4 or positions.shape[-1] != 3:
+        raise ValueError(f"{what}: positions of shape {tuple(positions.shape)}, expected [B, T, J, 3]")
+    B, T, J, _ = positions.shape
+    if J < 2 or J > 24:
+        raise ValueError(f"{what}: {J} joints outside 2..24")
+    if B < 1 or T < 1:
+        raise ValueError(f"{what}: {B} clips of {T} frames")
+    _, _, face, _, flat, starts, off = _encode_validate(what, (B, 2, J, 3), None, HML, chains, raw_offsets, face_joint_indx, (0, 0), (0, 0),
+                                                        None, None, None)
+    tgt = target_offset.detach().cpu().numpy() if torch.is_tensor(target_offset) else np.asarray(target_offset)
+    tgt = np.ascontiguousarray(tgt, dtype=np.float32)
+    if tgt.shape != (J, 3):
+        raise ValueError(f"{what}: target offsets of shape {tgt.shape}, expected ({J}, 3)")
+    legs = [int(i) for i in l_idx]
+    if len(legs) != 2 or min(legs) < 1 or max(legs) >= J:
+        raise ValueError(f"{what}: l_idx {list(l_idx)}: two joints of 1..{J - 1} are needed")
+    host = None
+    if lengths is not None:
+        host = lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)
+        host = host.reshape(-1).astype(np.int64)
+        if host.shape[0] != B:
+            raise ValueError(f"{what}: {host.shape[0]} lengths for {B} clips")
+        if host.min() < 1 or host.max() > T:
+            raise ValueError(f"{what}: lengths {host.min()}..{host.max()} outside 1..{T}")
+    if not positions.is_cuda or (torch.is_tensor(lengths) and not lengths.is_cuda):
+        raise RuntimeError(_NO_CPU.format(what))
+    limit = retarget_max_frames(J)
+    if T > limit:
+        raise RuntimeError(f"{what}: {T} frames > {limit}, the longest clip mst_retarget_joints takes (mst_retarget_max_frames({J}))")
+    dev = positions.device
+    pos = positions.detach().to(torch.float32).contiguous()
+    ld = None if host is None else torch.from_numpy(host.astype(np.int32)).to(dev)
+    out = torch.empty(B, T, J, 3, dtype=torch.float32, device=dev)
+    ints = lambda v: (C.c_int32 * max(len(v), 1))(*v)
+    floats = lambda a: (C.c_float * a.size)(*a.reshape(-1).tolist())
+    with torch.cuda.device(dev):
+        N.check(N.lib().mst_retarget_joints(N.ptr(pos), N.ptr(ld), B, T, J, ints(face), ints(flat), ints(starts), len(starts) - 1, floats(off),
+                                            floats(tgt), ints(legs), N.ptr(out), N.stream_ptr(dev)))
+    return out
+
+
+def uniform_skeleton_basic(positions, target_offset, n_raw_offsets, kinematic_chain, l_idx, face_joint_indx):
+    """The reference's `uniform_skeleton_basic`, positional signature: one clip [T, J, 3], numpy (numpy comes back) or a tensor."""
+    as_numpy = not torch.is_tensor(positions)
+    pos = torch.as_tensor(np.asarray(positions, dtype=np.float32)) if as_numpy else positions
+    if pos.dim() != 3:
+        raise ValueError(f"uniform_skeleton_basic: positions of shape {tuple(pos.shape)}, expected one clip [T, J, 3]")
+    if not pos.is_cuda and as_numpy and torch.cuda.is_available():
+        pos = pos.cuda()
+    out = retarget_joints(pos[None], target_offset, n_raw_offsets, kinematic_chain, l_idx, face_joint_indx)[0]
+    return out.cpu().numpy() if as_numpy else out

@@ -603,6 +603,73 @@ int mst_encode_motion(const float* positions_dev, const float* rotations_dev, co
  * bound is the same for every joint count and both modes.  -1 for joints outside 2..24 or a mode that is neither 0 nor 1. */
 int mst_encode_max_frames(int32_t joints, int32_t mode);
 
+/* -------------------------------------------------------------------------------------------
+ * Motion files.  What is left on the host is text: one parse of a BVH file into an array of channel values, one formatting pass out of
+ * one (utils/bvh.py).  Everything between runs here.
+ *
+ * mst_bvh_decode: what the reference's read_bvh does after the text is parsed (data_loaders/humanml/common/bvh_utils.py:222-295), for a
+ * batch of clips of one hierarchy in one launch, one workgroup per clip: Euler degrees -> radians -> eul2q (utils/rotation.py:344-361
+ * over angle_axis_to_quat, :327-341; sinf / cosf) in the file's rotation order, q(e0, axis0) (x) (q(e1, axis1) (x) q(e2, axis2)); the
+ * sign continuity of remove_quat_discontinuities (:666-683) as a prefix parity over the full-rate frames (wave ballot, per-wave carries
+ * through LDS, a carry across rounds of 256 frames); the [phase::stride] sub-sampling; quat_fk (:646-663: qnorm, file order).
+ * channels_dev: [batch][frames][channels] float32, not written.  lengths_dev: [batch] int32, 1 <= len <= frames, or NULL; the kernel
+ * clamps into that range.  Host arrays over the file's joints, End Sites included: parents_host (joint 0 is the root, -1; parents[j] < j),
+ * rot_cols_host / pos_cols_host (the column of a joint's first rotation / position channel, -1 for none: an End Site is the identity, a
+ * joint without position channels stands at its offset), offsets_host [joints][3], order_host[3] (0 / 1 / 2 = X / Y / Z rotation, a
+ * permutation).  scale multiplies offsets and position channels.  select_host: num_select <= 24 file joints in the caller's order, or
+ * NULL / 0 for all of them.  workspace_dev: [batch][frames][joints][11] float32 (the raw local quaternion, global quaternion and global
+ * position of the whole file skeleton; a lane reads only what it wrote itself).
+ * Outputs over J = num_select or joints and frames_out = ceil((frames - phase) / stride): rotations_dev [batch][frames_out][J][4]
+ * (w, x, y, z) -- the file's own signed local quaternion (Anim.quats, not normalised) where a joint's nearest selected ancestor is its file
+ * parent or nothing is selected, qinv(gr[ancestor]) (x) gr[j] where joints between them were skipped, gr[j] where it has no selected
+ * ancestor -- and positions_dev [batch][frames_out][J][3], the global positions: together what mst_encode_motion takes in POSROT.
+ * Optional (NULL: not written): local_positions_dev (Anim.pos) and global_rotations_dev.  Frames at or past a clip's length: exact zeros.
+ * Stated deviation: for a dot product of exactly 0 between neighbouring raw quaternions the reference takes the raw sign, the kernel keeps
+ * the running one.
+ * Refused here: joints outside 1 .. mst_bvh_max_joints, frames above mst_bvh_max_frames, channels outside 3 .. 6 * joints, a column outside
+ * the channels, parents that are no tree in file order, an order that is no permutation, stride < 1, phase outside 0 .. stride - 1 or past
+ * the frames, more than 24 selected joints, one out of range or named twice.
+ * ----------------------------------------------------------------------------------------- */
+int mst_bvh_decode(const float* channels_dev, const int32_t* lengths_dev, int32_t batch, int32_t frames, int32_t channels, int32_t joints,
+                   const int32_t* parents_host, const int32_t* rot_cols_host, const int32_t* pos_cols_host, const float* offsets_host,
+                   const int32_t* order_host, float scale, int32_t stride, int32_t phase, const int32_t* select_host, int32_t num_select,
+                   float* workspace_dev, float* rotations_dev, float* positions_dev, float* local_positions_dev,
+                   float* global_rotations_dev, void* stream);
+/* Most file joints (End Sites included) mst_bvh_decode and mst_quats_to_channels take: the skeleton's tables ride in the kernel arguments
+ * and a lane keeps one scan bit a joint in two 64-bit registers. */
+int mst_bvh_max_joints(void);
+/* Longest clip mst_bvh_decode takes.  Nothing a frame needs is kept in LDS, so the bound is the same for every joint count: one workgroup
+ * walks a clip 256 frames a round, 64 rounds at the cap of 16384.  -1 for joints outside 1 .. mst_bvh_max_joints. */
+int mst_bvh_max_frames(int32_t joints);
+
+/* The numbers the reference's save_bvh formats (bvh_utils.py:588-612), one thread per clip, frame and joint: qnorm, q2eul of order[::-1]
+ * (utils/rotation.py:364-382, its own formula set), degrees.  order: 0 = a 'zyx' file (q2eul 'xyz'; the default and what every caller in
+ * the reference uses), 1 = an 'xzy' file (q2eul 'yzx'); q2eul has no formulas for another.  quats_dev: [batch][frames][joints][4], need
+ * not be normalised; root_pos_dev: [batch][frames][3] -- JointFit.joint_quats and JointFit.r_pos as they are.  perm_host[joints]: output
+ * slot -> joint, the writer's save_joint_seq (perm[0] = 0).  positions_dev: NULL, or [batch][frames][joints][3] for a file written with
+ * positions=True.  out_dev: [batch][frames][3 + 3 * joints] -- the root position, then per slot the three angles in the file's channel
+ * order -- or, with positions, [batch][frames][6 * joints]: per slot the position (the root's: root_pos) and the angles.
+ * Refused here: joints outside 1 .. mst_bvh_max_joints, another order, a perm that is no permutation or does not start at the root. */
+int mst_quats_to_channels(const float* quats_dev, const float* root_pos_dev, const float* positions_dev, const int32_t* perm_host,
+                          int32_t batch, int32_t frames, int32_t joints, int32_t order, float* out_dev, void* stream);
+
+/* The reference's uniform_skeleton_basic (data_loaders/humanml/scripts/motion_process.py:12-35) for a batch, one workgroup per clip, one
+ * frame per lane: source offsets from frame 0 (Skeleton.get_offsets_joints, common/skeleton.py:43-51); the leg ratio from the largest
+ * absolute component of the two leg offsets, not their norms (the reference's quirk, kept); the root scaled by it; the chain IK of
+ * inverse_kinematics_np (:55-105; smooth_forward=False, frame 0's root quaternion the identity, every chain restarting from the root
+ * quaternion); forward_kinematics_np (:130-151) with the target offsets.  positions_dev / out_dev: [batch][frames][joints][3], distinct;
+ * lengths_dev: [batch] int32, 1 <= len <= frames, or NULL (clamped by the kernel); frames past a clip are exact zeros, as is a joint no
+ * chain places.  Host arrays as in mst_encode_motion: face_ids_host[4], the flattened chains, raw_offsets_host[joints][3]; and
+ * target_offsets_host[joints][3], leg_ids_host[2] (l_idx).  A zero-length bone divides by zero, here as in the reference.
+ * Refused here: joints outside 2..24, frames above mst_retarget_max_frames, a face id out of range or named twice, a chain that does not
+ * start at a placed joint or names a joint twice as a child, a leg joint outside 1 .. joints - 1, out_dev == positions_dev. */
+int mst_retarget_joints(const float* positions_dev, const int32_t* lengths_dev, int32_t batch, int32_t frames, int32_t joints,
+                        const int32_t* face_ids_host, const int32_t* chains_host, const int32_t* chain_starts_host, int32_t num_chains,
+                        const float* raw_offsets_host, const float* target_offsets_host, const int32_t* leg_ids_host, float* out_dev,
+                        void* stream);
+/* Longest clip mst_retarget_joints takes (nothing is kept on chip: the bound of mst_bvh_max_frames).  -1 for joints outside 2..24. */
+int mst_retarget_max_frames(int32_t joints);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
