@@ -33,6 +33,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_ik.h"
 #include "mst_encode.h"
 #include "mst_bvh.h"
+#include "mst_rotdec.h"
 #include "mst_window.h"
 #include "mst_plan.h"
 
@@ -3621,6 +3622,110 @@ extern "C" int mst_retarget_joints(const float* positions, const int32_t* length
     p.J = joints;
     x.out = out;
     hipLaunchKernelGGL(k_retarget, dim3(batch), dim3(kEncThreads), 0, (hipStream_t)stream, p, x);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// Rotation-channel decode (mst_rotdec.h).  Nothing a frame needs is kept in LDS (96 bytes of wave totals for the three scans), so the
+// frame bound is the same for every joint count; the joint bound is the chain state a lane keeps in scratch memory (16 floats a joint).
+extern "C" int mst_rot_decode_max_joints(void) { return kRotMaxJoints; }
+extern "C" int mst_rot_decode_max_frames(int32_t joints) {
+    if (joints < 2 || joints > kRotMaxJoints) {
+        fail("mst_rot_decode_max_frames: joints %d outside 2..%d", joints, kRotMaxJoints);
+        return -1;
+    }
+    return kRotMaxFrames;
+}
+extern "C" int mst_rot_decode(const float* data, int64_t stride_batch, int64_t stride_frame, int64_t stride_feat, const float* mean,
+                              const float* stdv, const int32_t* lengths, int32_t batch, int32_t frames, int32_t feats, int32_t joints,
+                              int32_t route, const int32_t* chains, const int32_t* chain_starts, int32_t num_chains, const float* offsets,
+                              const int32_t* face_ids, const float* raw_offsets, const int32_t* out_source, const int32_t* out_parents, int32_t out_joints, float* quats, float* root_pos,
+                              float* joint_pos, float* local_rows, void* stream) {
+    if (route != kRotHml && route != kRotReal && route != kRotPosIk)
+        return fail("mst_rot_decode: route %d is none of 0 (HML_ROT), 1 (REAL_ROT), 2 (POS_IK)", route);
+    if (joints < 2 || joints > kRotMaxJoints) return fail("mst_rot_decode: joints %d outside 2..%d (mst_rot_decode_max_joints)", joints, kRotMaxJoints);
+    const int want = route != kRotReal ? 12 * joints - 1 : 9 * joints + 1;
+    if (feats != want)
+        return fail("mst_rot_decode: feats %d != %s = %d, the row of route %d", feats, route != kRotReal ? "12 * joints - 1" : "9 * joints + 1", want, route);
+    if (frames < 1) return fail("mst_rot_decode: frames %d < 1", frames);
+    if (frames > kRotMaxFrames) return fail("mst_rot_decode: frames %d > %d (mst_rot_decode_max_frames)", frames, kRotMaxFrames);
+    if (batch < 1 || batch > 65535) return fail("mst_rot_decode: batch %d outside 1..65535", batch);
+    if (!data) return fail("mst_rot_decode: null data");
+    if ((mean == nullptr) != (stdv == nullptr)) return fail("mst_rot_decode: mean and std come together");
+    if (!chains || !chain_starts || num_chains < 1 || !offsets) return fail("mst_rot_decode: null skeleton (chains, chain starts, offsets)");
+    if (!quats && !root_pos && !joint_pos && !local_rows) return fail("mst_rot_decode: no output asked for");
+    if (local_rows && route != kRotReal) return fail("mst_rot_decode: the local rows (process_pos_from_real_rot) belong to route 1 (REAL_ROT)");
+    RotArgs p{};
+    {
+        bool placed[kRotMaxJoints] = {true};
+        for (int c = 0; c < num_chains; c++) {
+            const int lo = chain_starts[c], hi = chain_starts[c + 1];
+            if (lo < 0 || hi - lo < 2) return fail("mst_rot_decode: chain %d has fewer than two joints", c);
+            for (int k = lo; k < hi; k++)
+                if (chains[k] < 0 || chains[k] >= joints) return fail("mst_rot_decode: joint %d of chain %d outside 0..%d", chains[k], c, joints - 1);
+            if (!placed[chains[lo]]) return fail("mst_rot_decode: chain %d starts at joint %d, which no earlier chain has placed", c, chains[lo]);
+            for (int k = lo + 1; k < hi; k++) {
+                if (placed[chains[k]]) return fail("mst_rot_decode: joint %d is named twice as a child (chain %d)", chains[k], c);
+                placed[chains[k]] = true;
+                p.link_child[p.n_links] = (signed char)chains[k];
+                p.link_parent[p.n_links] = (signed char)chains[k - 1];
+                p.link_first[p.n_links] = k == lo + 1;
+                p.n_links++;
+            }
+        }
+        for (int j = 0; j < joints; j++)
+            if (!placed[j]) return fail("mst_rot_decode: joint %d is named by no chain", j);
+    }
+    if (route == kRotPosIk) {
+        if (!face_ids || !raw_offsets) return fail("mst_rot_decode: route 2 (POS_IK) needs the face joints and the raw offsets");
+        for (int i = 0; i < 4; i++) {
+            if (face_ids[i] < 0 || face_ids[i] >= joints) return fail("mst_rot_decode: face joint %d outside 0..%d", face_ids[i], joints - 1);
+            p.face[i] = face_ids[i];
+        }
+        for (int j = 0; j < joints; j++)
+            for (int k = 0; k < 3; k++) p.raw[j][k] = raw_offsets[3 * j + k];
+        // scipy.ndimage._gaussian_kernel1d(sigma 20, order 0, radius 80), in double
+        double sum = 0.0;
+        for (int k = -kRotRadius; k <= kRotRadius; k++) sum += exp(-0.5 / (20.0 * 20.0) * (double)(k * k));
+        for (int k = 0; k <= kRotRadius; k++) p.taps[k] = exp(-0.5 / (20.0 * 20.0) * (double)(k * k)) / sum;
+    }
+    if (route != kRotReal) {
+        if (quats) {
+            if (!out_source || !out_parents) return fail("mst_rot_decode: routes 0 and 2 write quaternions on the expanded skeleton: null gather map or parents");
+            if (out_joints < joints || out_joints > kRotMaxOut) return fail("mst_rot_decode: out_joints %d outside %d..%d", out_joints, joints, kRotMaxOut);
+            for (int i = 0; i < out_joints; i++) {
+                if (out_source[i] < -1 || out_source[i] >= joints)
+                    return fail("mst_rot_decode: out_source[%d] = %d names no joint of 0..%d (-1: identity)", i, out_source[i], joints - 1);
+                if (i && (out_parents[i] < 0 || out_parents[i] >= out_joints))
+                    return fail("mst_rot_decode: out_parents[%d] = %d outside 0..%d", i, out_parents[i], out_joints - 1);
+                p.src[i] = (signed char)out_source[i];
+                p.xparent[i] = (signed char)(i ? out_parents[i] : -1);
+            }
+        }
+        p.Jx = quats ? out_joints : joints;
+    } else {
+        if (out_joints != joints) return fail("mst_rot_decode: route 1 writes the J local quaternions: out_joints %d != joints %d", out_joints, joints);
+        p.Jx = joints;
+    }
+    for (int j = 0; j < joints; j++)
+        for (int k = 0; k < 3; k++) p.off[j][k] = offsets[3 * j + k];
+    p.data = data;
+    p.sb = stride_batch;
+    p.st = stride_frame;
+    p.sf = stride_feat;
+    p.mean = mean;
+    p.stdv = stdv;
+    p.lengths = lengths;
+    p.B = batch;
+    p.T = frames;
+    p.J = joints;
+    p.mode = route;
+    p.quats = quats;
+    p.root_pos = root_pos;
+    p.joints = joint_pos;
+    p.local = local_rows;
+    const size_t lds = route == kRotPosIk ? sizeof(float) * 2 * frames : 0;      // at most 32 KB: below the opt-in threshold
+    hipLaunchKernelGGL(k_rot_decode, dim3(batch), dim3(kRotThreads), lds, (hipStream_t)stream, p);
     HIPCHECK(hipGetLastError());
     return 0;
 }

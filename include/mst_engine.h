@@ -670,6 +670,50 @@ int mst_retarget_joints(const float* positions_dev, const int32_t* lengths_dev, 
 /* Longest clip mst_retarget_joints takes (nothing is kept on chip: the bound of mst_bvh_max_frames).  -1 for joints outside 2..24. */
 int mst_retarget_max_frames(int32_t joints);
 
+/* -------------------------------------------------------------------------------------------
+ * A sample's rotation channels decoded, one launch for a batch, one workgroup per clip: recover_root_rot_pos
+ * (data_loaders/humanml/common/bvh_utils.py:1299-1318; the angle an exclusive, root x and z inclusive prefix sums, taken in double by a
+ * workgroup scan and rounded to fp32 once per frame) followed by one route.
+ * route 0, HML_ROT, feats = 12 * joints - 1 (263 at 22 joints): output_bvh (bvh_utils.py:1382-1441) -- the joints - 1 6D blocks at feature
+ * 4 + 3 * (joints - 1) through cont6d2q (common/rotation.py:744-776), world quaternions chain by chain, every chain restarting from
+ * r_rot_quat, gathered onto the expanded skeleton and made local, qinv(world[parent]) (x) world[i] -- and recover_from_rot (:1321-1335;
+ * Skeleton.forward_kinematics_cont6d, common/skeleton.py:177-198).
+ * route 2, POS_IK, the same 12 * joints - 1 row read for its positions: output_bvh_with_pos (:1444-1511) -- recover_from_ric (:1348-1363),
+ * Skeleton.inverse_kinematics_np(smooth_forward=True) (common/skeleton.py:55-103; the forward direction smoothed by 161 taps summed in
+ * double, as mst_encode_motion does), the IK's root dropped, then route 0's chain products and expanded skeleton; joints_dev receives
+ * recover_from_ric's positions.  face_ids_host[4] = r_hip, l_hip, sdr_r, sdr_l and raw_offsets_host[joints][3], the unit bone
+ * directions, belong to this route (NULL otherwise).  A zero-length bone divides by zero, here as in the reference.
+ * route 1, REAL_ROT, feats = 9 * joints + 1 (181 / 190): output_bvh_from_real_rot (:1538-1563; joints 6D blocks through cont6d2q, the
+ * root's multiplied from the left by r_rot_quat), recover_from_real_rot (:1337-1345; forward_kinematics_real_cont6d, skeleton.py:200-222)
+ * and process_pos_from_real_rot (:1366-1378; root-relative rows; stated deviation: the reference subtracts the root's x and z in place from the
+ * storage it reads, so what it returns depends on how torch splits the loop, and a short clip loses the subtraction altogether).
+ * data_dev: element (b, t, f) at data_dev[b * stride_batch + t * stride_frame + f * stride_feat], as mst_fit_joints reads it; mean_dev /
+ * std_dev: [feats], both or neither, applied as x * std + mean.  lengths_dev: [batch] int32, 1 <= len <= frames, or NULL; the kernel clamps
+ * the values into that range, so no access leaves a clip (the Python handle checks them).  The kinematic chains flattened as in
+ * mst_encode_motion; every joint 1 .. joints - 1 is a child of exactly one chain.  offsets_host: [joints][3], the bone offsets of the
+ * forward kinematics (row 0 unused).  Routes 0 and 2: out_source_host[out_joints], expanded joint -> the joint whose world quaternion it carries
+ * (-1: the identity), and out_parents_host[out_joints] (entry 0 ignored) -- both a pure function of the chains, formed on the host; they
+ * are read only when quats_dev is given.  Route 1: out_joints = joints, both NULL.
+ * Outputs, each optional (NULL: not written), at least one: quats_dev [batch][frames][out_joints][4] local quaternions (w, x, y, z),
+ * root_pos_dev [batch][frames][3], joints_dev [batch][frames][joints][3], local_dev [batch][frames][3 * (joints - 1)] (route 1 only).
+ * Rows at or past a clip's length: exact zeros.  Not reproduced: rotm2axangle's SVD branch for an angle that is an exact multiple of pi.
+ * Refused here: a route that is none of the three, route 2 without face joints or raw offsets or with a face joint outside the skeleton, joints outside 2 .. mst_rot_decode_max_joints, feats that are not the route's, frames < 1 or above
+ * mst_rot_decode_max_frames, batch outside 1..65535, null data or skeleton, one of mean / std without the other, no output, local_dev on
+ * route 0, a chain shorter than two joints, starting at a joint not yet placed, or naming a joint outside the skeleton or twice as a
+ * child, a joint no chain names, out_joints out of range, a gather map that names a joint >= joints, a parent outside the expanded skeleton.
+ * ----------------------------------------------------------------------------------------- */
+int mst_rot_decode(const float* data_dev, int64_t stride_batch, int64_t stride_frame, int64_t stride_feat, const float* mean_dev,
+                   const float* std_dev, const int32_t* lengths_dev, int32_t batch, int32_t frames, int32_t feats, int32_t joints,
+                   int32_t route, const int32_t* chains_host, const int32_t* chain_starts_host, int32_t num_chains,
+                   const float* offsets_host, const int32_t* face_ids_host, const float* raw_offsets_host,
+                   const int32_t* out_source_host, const int32_t* out_parents_host, int32_t out_joints,
+                   float* quats_dev, float* root_pos_dev, float* joints_dev, float* local_dev, void* stream);
+/* Most joints mst_rot_decode takes: a lane keeps 16 floats a joint of chain state in scratch memory (24 joints: 1536 bytes a lane). */
+int mst_rot_decode_max_joints(void);
+/* Longest clip mst_rot_decode takes: LDS holds the scans' wave totals alone (96 bytes), so the bound is time -- 16 rounds of 256 frames
+ * at the cap of 4096, what the windowed loops return.  -1 for joints outside 2 .. mst_rot_decode_max_joints. */
+int mst_rot_decode_max_frames(int32_t joints);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
