@@ -14,6 +14,7 @@
 #pragma once
 #include "mst_common.h"
 #include "mst_gemm_dma.h"
+#include "mst_plan.h"
 
 #ifndef EMB_MARK            // diagnostic builds (tools/experiments/r4_embed_stamps.py) stamp the phases; the product build has none
 #define EMB_MARK(i)
@@ -281,7 +282,8 @@ __global__ __launch_bounds__(512) void k_embed_out(RowsFrames xs, const f16* __r
     // is drawn up front only where the registers allow (one accumulator set)
     constexpr int NU = 4 * NBW;                                        // ceil(128 NBW features x 16 frame groups / 512 threads)
     constexpr bool EARLY_NOISE = NX == 1;
-    const bool staged = MODE != 0 && NBW <= 3 && (epi.T & 3) == 0;     // (4 blocks per wave = 16 items per thread: too many registers)
+    constexpr bool CAN_STAGE = embed_out_can_stage(NBW, MODE);         // (mst_plan.h: embed_out_staged, the rule the launch plan reports, one copy)
+    const bool staged = CAN_STAGE && embed_out_frames_stage(epi.T);
     OutItems<MODE == 0 ? 1 : MODE, MODE == 0 ? 1 : NU> items;
     if constexpr (MODE != 0) items.init(epi, tok0);
 

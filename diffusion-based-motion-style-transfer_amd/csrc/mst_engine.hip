@@ -353,8 +353,7 @@ extern "C" int mst_engine_create(const mst_config* c, mst_engine** out) {
     // rows of every token-row buffer: whole 256-row tiles plus one spare tile -- a slice starts at an arbitrary row and
     // its last tile may over-READ up to a tile beyond the slice (never write)
     e->M_pad = (int)(((M + 255) / 256) * 256) + 256;
-    e->kin_pad = ((c->feats + 31) / 32) * 32;           // K of the pose-embedding GEMM: whole 32-deep slabs,
-    if (e->kin_pad < 96) e->kin_pad = 96;               // and at least the 3 slabs the ring keeps in flight
+    e->kin_pad = embed_kin_pad(c->feats);               // K of the pose-embedding GEMM (mst_plan.h)
     e->nt_out = (c->feats + 255) / 256;              // output-projection tile = 256 * nt_out features
     e->fout_pad = e->nt_out * 256;
     for (int l = 0; l < c->num_layers; l++) {
@@ -948,7 +947,8 @@ static WS ws_slice(const mst_engine* e, int r0, int T) {
 
 // Packed weight copies of the two fused kernels, refreshed where stale: on the stream the sampling launch is about to use (the caller
 // orders that stream behind its weight uploads, as for the plain matrices).
-static int embed_out_nbw(const mst_engine* e) { return (e->cfg.feats + 127) / 128; }     // 16-feature blocks per wave of k_embed_out
+static int embed_out_nbw(const mst_engine* e) { return embed_out_nbw(e->cfg.feats); }     // 16-feature blocks per wave of k_embed_out (mst_plan.h)
+static_assert(EMBED_BT == EmbCfg::BT && EMBED_SMEM == EmbCfg::SMEM, "mst_plan.h plans the projections for mst_embed.h's tile and LDS budget");
 // (layers = false: the training node's model calls -- they run the two projections' fast kernels but read the layers' plain matrices,
 // and every fine-tune iteration re-uploads those: their packed copies are made only when a sampling launch follows)
 // (on the stream every slice of a loop forks from: mst_sample_loop packs before the fork, so no slice reads fragments another stream is still writing)
@@ -1418,8 +1418,8 @@ static int launch_embed_in_n(mst_engine* e, const WS& ws, int tot, const DEpiEmb
     HIPCHECK(hipGetLastError());
     return 0;
 }
-static int launch_embed_in(mst_engine* e, const WS& ws, int tot, const DEpiEmbedIn& epi, hipStream_t st) {
-    switch (e->kin_pad / 32) {
+static int launch_embed_in(mst_engine* e, const WS& ws, int tot, const DEpiEmbedIn& epi, const EmbedInPlan& ip, hipStream_t st) {
+    switch (ip.ks) {
 #define EI(K_) case K_: return launch_embed_in_n<K_>(e, ws, tot, epi, st);
         EI(3) EI(4) EI(5) EI(6) EI(7) EI(8) EI(9) EI(10) EI(11) EI(12) EI(13) EI(14) EI(15) EI(16)
 #undef EI
@@ -1457,7 +1457,8 @@ static int assemble_stream(mst_engine* e, const WS& ws, const float* x, int clip
             HIPCHECK(hipGetLastError());
         }
         const DEpiEmbedIn epi = embed_in_epi(e, ws, clips_x, rows, T, temb_uniform_row, temb_mod, tp_uncond, lr.ld, lr.joff, tidx_table, pe_dropout);
-        if (e->embed_fast && !e->precise) return launch_embed_in(e, ws, tot, epi, st);
+        const EmbedInPlan ip = plan_embed_in(F, e->precise, e->embed_fast);
+        if (ip.kernel == EMBED_LATENCY) return launch_embed_in(e, ws, tot, epi, ip, st);
         // x_t as hi + lo (RowsDirect::Xlo): both halves of a k-slab beside ONE copy of the weight slab
         CHECK((launch_gemm_dma<64, 512, 2, 2, 4, 1, 32, 2>(dim3((tot + 63) / 64, 1), RowsDirect{ws.xt, e->kin_pad, ws.xt_lo, e->precise ? e->w_pose_in_lo : nullptr},
                                                           e->w_pose_in, e->kin_pad, e->kin_pad, epi, st)));
@@ -1612,12 +1613,13 @@ static int launch_out(mst_engine* e, const WS& ws, int batch, int T, float* out,
     return launch_gemm_dma<64, BF, MT, NT, 4, NX, 32, XS>(dim3((batch * T + 63) / 64, 1), xs, w_override ? w_override : e->w_pose_out, MST_D, MST_D, epi, st);
 }
 template <int MODE, int BF, int MT, int NT>
-static int launch_out_nx(mst_engine* e, const WS& ws, int cfg, int batch, int T, float* out, const StepArgs& sa, hipStream_t st,
+static int launch_out_nx(mst_engine* e, const WS& ws, const EmbedOutPlan& op, int batch, int T, float* out, const StepArgs& sa, hipStream_t st,
                          const f16* wo = nullptr, const float* bo = nullptr, int tok_off = 1, bool frames_next = false, bool hi_lo = false) {
+    const bool cfg = op.nx == 2;
     // hi + lo stream: both halves of a k-slab beside one copy of the weight slab where that ring fits the LDS (<= 384 rows),
     // otherwise the K range twice (gemm_mainloop_dma)
     if constexpr (BF <= 384) {
-        if (hi_lo) return cfg ? launch_out<MODE, BF, MT, NT, 2, 2>(e, ws, batch, T, out, sa, st, wo, bo, tok_off, frames_next, true)
+        if (op.ring_xs == 2) return cfg ? launch_out<MODE, BF, MT, NT, 2, 2>(e, ws, batch, T, out, sa, st, wo, bo, tok_off, frames_next, true)
                               : launch_out<MODE, BF, MT, NT, 1, 2>(e, ws, batch, T, out, sa, st, wo, bo, tok_off, frames_next, true);
     }
     return cfg ? launch_out<MODE, BF, MT, NT, 2>(e, ws, batch, T, out, sa, st, wo, bo, tok_off, frames_next, hi_lo)
@@ -1630,14 +1632,8 @@ static int launch_embed_out_n(mst_engine* e, const RowsFrames& xs, const DEpiEmb
     HIPCHECK(hipGetLastError());
     return 0;
 }
-// Can a sampling step's output projection also embed the NEXT step (k_embed_out<.., KSN>)?  The shapes the reference's datasets have
-// (150 / 181 / 190 / 263 features: 5 / 6 / 6 / 9 k-steps), and the tile plus the two frame images must fit the LDS.
-static bool embed_next_fits(const mst_engine* e, int T) {
-    const int ks = e->kin_pad / 32, nbw = (e->cfg.feats + 127) / 128, F = e->cfg.feats;
-    if (!e->embed_fast || e->precise || (T & 3)) return false;
-    if (!((ks == 5 && nbw == 2) || (ks == 6 && nbw == 2) || (ks == 9 && nbw == 3))) return false;
-    return (size_t)F * (EmbCfg::BT + 4) * 4 + 16 + 2 * (size_t)EmbCfg::BT * (ks * 64 + 16) <= (size_t)EmbCfg::SMEM;
-}
+// Can a sampling step's output projection also embed the NEXT step (k_embed_out<.., KSN>)?  embed_next_ksn of mst_plan.h.
+static bool embed_next_fits(const mst_engine* e, int T) { return embed_next_ksn(e->cfg.feats, T, e->precise, e->embed_fast) != 0; }
 template <int MODE, int NBW, int KSN>
 static int launch_embed_step_n(mst_engine* e, const RowsFrames& xs, const DEpiEmbedOut<MODE>& epi, const DEpiEmbedIn& next, int tiles, hipStream_t st) {
     CHECK(ensure_dyn_lds((const void*)k_embed_out<NBW, MODE, 1, KSN>, EmbCfg::SMEM));
@@ -1646,18 +1642,18 @@ static int launch_embed_step_n(mst_engine* e, const RowsFrames& xs, const DEpiEm
     return 0;
 }
 template <int MODE>
-static int launch_embed_out(mst_engine* e, const WS& ws, int cfg, int batch, int T, float* out, const StepArgs& sa, hipStream_t st,
+static int launch_embed_out(mst_engine* e, const WS& ws, const EmbedOutPlan& op, int batch, int T, float* out, const StepArgs& sa, hipStream_t st,
                             int tok_off, bool frames_next, const DEpiEmbedIn* next = nullptr) {
     const int S = T + tok_off, tiles = (batch * T + EmbCfg::BT - 1) / EmbCfg::BT;
     RowsFrames xs{ws.hx, MST_D, T, S, batch * T, EmbCfg::BT, (size_t)batch * S, tok_off, ws.hl, nullptr};
     DEpiEmbedOut<MODE> epi{e->b_pose_out, e->cfg.feats, T, batch * T, out, sa};
     if (frames_next) { epi.xt_next = ws.xt; epi.kpad = e->kin_pad; epi.xt_next_lo = ws.xt_lo; }
-    const int nbw = embed_out_nbw(e);
+    const bool cfg = op.nx == 2;
     if constexpr (MODE != 0) {
         if (next) {                                         // (mst_sample_loop asked embed_next_fits first)
             if (cfg || tok_off != 1) return fail("output projection: the fused next-step embedding is for plain sampling steps");
             epi.xt_next = ws.xt; epi.kpad = e->kin_pad;     // (marks the tile as reusable: OutItems::apply writes x_{t-1} back into it)
-            switch (e->kin_pad / 32) {
+            switch (op.ksn) {
                 case 5: return launch_embed_step_n<MODE, 2, 5>(e, xs, epi, *next, tiles, st);
                 case 6: return launch_embed_step_n<MODE, 2, 6>(e, xs, epi, *next, tiles, st);
                 case 9: return launch_embed_step_n<MODE, 3, 9>(e, xs, epi, *next, tiles, st);
@@ -1666,7 +1662,7 @@ static int launch_embed_out(mst_engine* e, const WS& ws, int cfg, int batch, int
         }
     }
 #define EO(N_) case N_: return cfg ? launch_embed_out_n<MODE, N_, 2>(e, xs, epi, tiles, st) : launch_embed_out_n<MODE, N_, 1>(e, xs, epi, tiles, st);
-    switch (nbw) { EO(1) EO(2) EO(3) case 4: return launch_embed_out_n<MODE, 4, 1>(e, xs, epi, tiles, st); }
+    switch (op.nbw) { EO(1) EO(2) EO(3) case 4: return launch_embed_out_n<MODE, 4, 1>(e, xs, epi, tiles, st); }
 #undef EO
     return fail("output projection: %d features unsupported", e->cfg.feats);
 }
@@ -1675,13 +1671,13 @@ static int launch_out_nt(mst_engine* e, const WS& ws, int cfg, int batch, int T,
                          const f16* wo = nullptr, const float* bo = nullptr, int tok_off = 1, bool frames_next = false, bool hi_lo = false,
                          const DEpiEmbedIn* next = nullptr) {
     ProfScope ps(e, FAM_EMBED_OUT, st);
-    if (e->embed_fast && !e->precise && hi_lo && !wo && !bo && !(cfg && embed_out_nbw(e) == 4))      // (385+ features under CFG: its two accumulator sets spill)
-        return launch_embed_out<MODE>(e, ws, cfg, batch, T, out, sa, st, tok_off, frames_next, next);
+    const EmbedOutPlan op = plan_embed_out(e->cfg.feats, T, cfg, e->precise, e->embed_fast, MODE, hi_lo, wo || bo);
+    if (op.kernel == EMBED_LATENCY) return launch_embed_out<MODE>(e, ws, op, batch, T, out, sa, st, tok_off, frames_next, next);
     if (next) return fail("output projection: the fused next-step embedding needs the fast embed kernels");
-    const int rows_out = e->cfg.feats;                   // (also for the pose embedding's backward, which runs this kernel with W_in^T)
-    if (rows_out <= 256) return launch_out_nx<MODE, 256, 2, 1>(e, ws, cfg, batch, T, out, sa, st, wo, bo, tok_off, frames_next, hi_lo);
-    if (rows_out <= 384) return launch_out_nx<MODE, 384, 1, 3>(e, ws, cfg, batch, T, out, sa, st, wo, bo, tok_off, frames_next, hi_lo);
-    return launch_out_nx<MODE, 512, 2, 2>(e, ws, cfg, batch, T, out, sa, st, wo, bo, tok_off, frames_next, hi_lo);
+    // (the ring also runs the pose embedding's backward, with W_in^T)
+    if (op.ring_bf == 256) return launch_out_nx<MODE, 256, 2, 1>(e, ws, op, batch, T, out, sa, st, wo, bo, tok_off, frames_next, hi_lo);
+    if (op.ring_bf == 384) return launch_out_nx<MODE, 384, 1, 3>(e, ws, op, batch, T, out, sa, st, wo, bo, tok_off, frames_next, hi_lo);
+    return launch_out_nx<MODE, 512, 2, 2>(e, ws, op, batch, T, out, sa, st, wo, bo, tok_off, frames_next, hi_lo);
 }
 
 // the switches mst_plan.h decides by, as they stand now (mst_set_precise, mst_set_trunk_groups and mst_debug_stop_after change them between calls)

@@ -1,6 +1,7 @@
 // The launch plan of the sampling path: which kernels a launch sequence runs, at what tile height, and in how many clip slices a loop
-// runs.  Host-only plain C++ (no HIP header, no f16): every launcher of mst_engine.hip follows it, tests/plan_mirror.py mirrors it, and
-// tests/test_launch_plan_cpu.py compares the two on the CPU through a driver that includes only this file.
+// runs.  Plain C++ for the host (no HIP header, no f16; k_embed_out alone reads the constexpr rules of embed_out_staged): every launcher
+// of mst_engine.hip follows it, tests/plan_mirror.py mirrors it, and tests/test_launch_plan_cpu.py compares the two on the CPU through
+// a driver that includes only this file.
 #pragma once
 
 namespace mst {
@@ -92,6 +93,69 @@ inline int plan_slices(const PlanKnobs& k, int batch, int cfg, int frames) {
     }
     while (n > 1 && rows / n < 8) n--;                       // at least 8 rows through the transformer per slice
     return n;
+}
+
+// ------------------------------------------------------------------------------ the two projections (K3, K9)
+// The latency kernels of mst_embed.h work on 64-frame tiles inside this much dynamic LDS (EmbCfg::BT / EmbCfg::SMEM: mst_engine.hip
+// asserts that they match).
+constexpr int EMBED_BT = 64, EMBED_SMEM = 160 * 1024;
+
+// EMBED_LATENCY: k_embed_in<KS> / k_embed_out<NBW, MODE, NX, KSN> (mst_embed.h); EMBED_RING: the slab ring (launch_gemm_dma), which
+// also multiplies split WEIGHTS (precise mode) and a caller's weight (the pose embedding's backward).
+enum EmbedKernel { EMBED_LATENCY = 0, EMBED_RING };
+
+// K of the pose-embedding GEMM: whole 32-deep slabs, and at least the 3 slabs the ring keeps in flight.
+inline int embed_kin_pad(int feats) { const int k = (feats + 31) / 32 * 32; return k < 96 ? 96 : k; }
+// 16-feature blocks per wave of k_embed_out: eight waves own blocks w, w + 8, ...
+inline int embed_out_nbw(int feats) { return (feats + 127) / 128; }
+
+struct EmbedInPlan { int kin_pad, ks /* k_embed_in<KS> */, kernel /* EmbedKernel */; };
+inline EmbedInPlan plan_embed_in(int feats, int precise, int embed_fast) {
+    const int kp = embed_kin_pad(feats);
+    return EmbedInPlan{kp, kp / 32, embed_fast && !precise ? EMBED_LATENCY : EMBED_RING};
+}
+
+// Can a sampling step's output projection also embed the NEXT step (k_embed_out<.., KSN>)?  The shapes the reference's datasets have
+// (150 / 181 / 190 / 263 features: 5 / 6 / 6 / 9 k-steps), frame counts the staged epilogue takes, and the tile plus the two frame
+// images must fit the LDS.  Returns KSN, or 0.
+inline int embed_next_ksn(int feats, int T, int precise, int embed_fast) {
+    const int ks = embed_kin_pad(feats) / 32, nbw = embed_out_nbw(feats);
+    if (!embed_fast || precise || (T & 3)) return 0;
+    if (!((ks == 5 && nbw == 2) || (ks == 6 && nbw == 2) || (ks == 9 && nbw == 3))) return 0;
+    return (long long)feats * (EMBED_BT + 4) * 4 + 16 + 2LL * EMBED_BT * (ks * 64 + 16) <= (long long)EMBED_SMEM ? ks : 0;
+}
+
+// Which epilogue k_embed_out<NBW, MODE, ..> runs: the staged one (OutItems) on a diffusion step, up to three blocks per wave (4 blocks =
+// 16 items per thread: too many registers), whose frame count is a multiple of 4 (a float4 never straddles a clip); else
+// DEpiEmbedOut::finish.  The kernel decides by itself, per launch, from THESE two rules (constexpr: hipcc compiles them for the device
+// too; the first is a constant of the instantiation), so the plan below and the kernel cannot drift apart.
+constexpr bool embed_out_can_stage(int nbw, int mode) { return mode != 0 && nbw <= 3; }
+constexpr bool embed_out_frames_stage(int T) { return (T & 3) == 0; }
+constexpr bool embed_out_staged(int nbw, int mode, int T) { return embed_out_can_stage(nbw, mode) && embed_out_frames_stage(T); }
+
+struct EmbedOutPlan {
+    int kernel;                 // EmbedKernel
+    int nbw, nx, staged;        // EMBED_LATENCY: k_embed_out<NBW, MODE, NX>; `staged`: embed_out_staged, as the kernel will find it
+    int ksn;                    // ... and the KSN of the fused next-step embedding a plain loop step may ask for (0: none)
+    int ring_bf, ring_xs;       // EMBED_RING: launch_out_nx<MODE, BF, ..> and its XS (2: hi and lo of a k-slab beside one weight slab)
+};
+// mode: DEpiEmbedOut<MODE> (0 = the model output alone); hi_lo: the stream is a split pair (ws.hx / ws.hl); custom_w: a caller's weight
+// or bias (the pose embedding's backward).
+inline EmbedOutPlan plan_embed_out(int feats, int T, int cfg, int precise, int embed_fast, int mode, int hi_lo, int custom_w) {
+    EmbedOutPlan p{};
+    const int nbw = embed_out_nbw(feats);
+    p.nx = cfg ? 2 : 1;
+    if (embed_fast && !precise && hi_lo && !custom_w && !(cfg && nbw == 4)) {        // (385+ features under CFG: its two accumulator sets spill)
+        p.kernel = EMBED_LATENCY;
+        p.nbw = nbw;
+        p.staged = embed_out_staged(nbw, mode, T);
+        p.ksn = mode != 0 && !cfg ? embed_next_ksn(feats, T, precise, embed_fast) : 0;
+        return p;
+    }
+    p.kernel = EMBED_RING;
+    p.ring_bf = feats <= 256 ? 256 : feats <= 384 ? 384 : 512;
+    p.ring_xs = hi_lo && p.ring_bf <= 384 ? 2 : 1;                 // (512 rows: the ring no longer fits the LDS twice; the K range runs twice)
+    return p;
 }
 
 // Slice i of `batch` clips in n slices: the last one may be short, and clips <= 0 means the slice is empty.

@@ -1,8 +1,9 @@
 """The one Python mirror of the sampling path's launch plan (csrc/mst_plan.h) and of the defaults it is called with.
 
-plan_trunk / rows_ntb / plan_slices / slice_of restate the header function by function; tests/test_launch_plan_cpu.py compares them
-with the header itself, field by field, on the CPU.  The names below them (plain_path, trunk_path, slices, loop_slices, slices_of) are
-what the GPU test modules put into their case ids and path tables."""
+plan_trunk / rows_ntb / plan_slices / slice_of and plan_embed_in / embed_next_ksn / plan_embed_out restate the header function by
+function; tests/test_launch_plan_cpu.py compares them with the header itself, field by field, on the CPU.  The names below them
+(embed_in_kernel, embed_out_kernel, plain_path, trunk_path, slices, loop_slices, slices_of) are what the GPU test modules put into
+their case ids and path tables."""
 
 # csrc/mst_engine.hip defaults
 SMALL_M = 1900                          # small_m (MST_SMALL_M): launches of at most this many token rows take the small path
@@ -78,6 +79,68 @@ def slice_of(batch, n, i):
     per = -(-batch // n)
     c0 = i * per
     return c0, per if c0 + per <= batch else batch - c0
+
+
+# ------------------------------------------------------------------------------ the two projections (K3, K9)
+EMBED_BT, EMBED_SMEM = 64, 160 * 1024                                    # EmbCfg::BT / EmbCfg::SMEM
+EMBED_KERNELS = ("latency", "ring")                                      # EmbedKernel
+EMBED_IN_FIELDS = ("kin_pad", "ks", "kernel")                            # EmbedInPlan
+EMBED_OUT_FIELDS = ("kernel", "nbw", "nx", "staged", "ksn", "ring_bf", "ring_xs")      # EmbedOutPlan
+
+
+def embed_kin_pad(feats):
+    return max(96, -(-feats // 32) * 32)
+
+
+def embed_out_nbw(feats):
+    return -(-feats // 128)
+
+
+def plan_embed_in(feats, precise=False, embed_fast=True):
+    """mst::plan_embed_in: EmbedInPlan as a dict (kernel as an index into EMBED_KERNELS)."""
+    kp = embed_kin_pad(feats)
+    return dict(kin_pad=kp, ks=kp // 32, kernel=EMBED_KERNELS.index("latency" if embed_fast and not precise else "ring"))
+
+
+def embed_next_ksn(feats, T, precise=False, embed_fast=True):
+    """mst::embed_next_ksn: KSN of the fused next-step embedding, or 0."""
+    ks, nbw = embed_kin_pad(feats) // 32, embed_out_nbw(feats)
+    if not embed_fast or precise or T % 4:
+        return 0
+    if (ks, nbw) not in ((5, 2), (6, 2), (9, 3)):
+        return 0
+    return ks if feats * (EMBED_BT + 4) * 4 + 16 + 2 * EMBED_BT * (ks * 64 + 16) <= EMBED_SMEM else 0
+
+
+def plan_embed_out(feats, T, cfg=False, precise=False, embed_fast=True, mode=0, hi_lo=True, custom_w=False):
+    """mst::plan_embed_out: EmbedOutPlan as a dict."""
+    nbw = embed_out_nbw(feats)
+    p = dict.fromkeys(EMBED_OUT_FIELDS, 0)
+    p["nx"] = 2 if cfg else 1
+    if embed_fast and not precise and hi_lo and not custom_w and not (cfg and nbw == 4):
+        p.update(kernel=EMBED_KERNELS.index("latency"), nbw=nbw, staged=int(mode != 0 and nbw <= 3 and T % 4 == 0),
+                 ksn=embed_next_ksn(feats, T, precise, embed_fast) if mode != 0 and not cfg else 0)
+        return p
+    bf = 256 if feats <= 256 else 384 if feats <= 384 else 512
+    p.update(kernel=EMBED_KERNELS.index("ring"), ring_bf=bf, ring_xs=2 if hi_lo and bf <= 384 else 1)
+    return p
+
+
+def embed_in_kernel(feats, precise=False):
+    """The pose embedding a sampling launch runs, by name."""
+    p = plan_embed_in(feats, precise)
+    return f"k_embed_in<{p['ks']}>" if EMBED_KERNELS[p["kernel"]] == "latency" else f"ring-in<kpad {p['kin_pad']}>"
+
+
+def embed_out_kernel(feats, T, cfg=False, precise=False, mode=0, fused_next=False):
+    """The output projection of a sampling launch over the last (split) stream, by name; fused_next: the step also embeds the next."""
+    p = plan_embed_out(feats, T, cfg, precise, True, mode)
+    if EMBED_KERNELS[p["kernel"]] == "ring":
+        return f"launch_out_nx<{mode}, {p['ring_bf']}, NX {p['nx']}, XS {p['ring_xs']}>"
+    if fused_next:
+        assert p["ksn"], (feats, T, mode)
+        return f"k_embed_out<{p['nbw']}, {mode}, 1, {p['ksn']}>"
+    return f"k_embed_out<{p['nbw']}, {mode}, {p['nx']}>"
 
 
 # ------------------------------------------------------------------------------ what the GPU tests name their cases by

@@ -11,6 +11,7 @@ import torch
 
 import mst_amd  # noqa: F401
 from mst_amd import synthetic as syn
+import token_profile as tp
 from conftest import SEED, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -445,6 +446,14 @@ def test_full_size_properties(tile_path):
     # same kernels (large-tile path forced): identical up to fp32 reduction noise; with the default small-tile path the two
     # clips run through differently tiled kernels -- two f16-operand evaluations of the same function
     assert rel_l2(part.cpu().numpy(), full[10:12].cpu().numpy()) < (1e-6 if tile_path == "0" else TOL)
+    # ... and those two clips of the batch-64 launch per clip, per token and per feature row against the oracle and its f16-operand
+    # rounding model (tests/token_profile.py): 2 of 64 clips weigh 3 % in a pooled figure.  (This test loads no golden vectors, so the
+    # fp32 oracle on the same inputs is the reference; test_cfg_at_headline_size_hml below takes the golden itself.)
+    from oracle import denoiser
+    pe = syn.positional_table(5000, 512)
+    ref, model = tp.rounding_model(denoiser.forward, w, pe, x0[10:12].cpu().numpy(), t[10:12].cpu().numpy(), txt[10:12].cpu().numpy())
+    print("batch-64 forward, clips 10..11", tile_path, tp.assert_profiles(full[10:12].cpu().numpy(), ref, model, tp.C_TOK, tp.C_ROW,
+                                                                          what=f"batch-64 forward, clips 10..11 ({tile_path})"))
 
 
 # ------------------------------------------------------------------------------ BASELINE.json configs[4] and configs[2] at full size
@@ -518,6 +527,12 @@ def test_cfg_at_headline_size_hml(golden, tile_path):
     e = rel_l2(out[:2].cpu().numpy(), golden["denoise"]["hml|cfg"])
     print("cfg64", tile_path, e)
     assert e < TOL
+    # the same two clips per clip, per token and per feature row: the golden as the reference, the oracle's f16-operand rounding
+    # model on the golden's inputs as the bar (tests/token_profile.py)
+    from oracle import denoiser
+    model = denoiser.cfg_forward(w, syn.positional_table(5000, 512), x[:2], t[:2], txt[:2], scale[:2], dt=torch.float16).numpy()
+    print("cfg64 profiles", tile_path, tp.assert_profiles(out[:2].cpu().numpy(), golden["denoise"]["hml|cfg"], model, tp.C_TOK, tp.C_ROW,
+                                                          what=f"cfg64, golden clips ({tile_path})"))
     assert torch.equal(out, eng.forward(cu(x), cu(t), scale=cu(scale), cfg=True))
     eng.set_text(cu(txt[30:32]), cfg=True)
     part = eng.forward(cu(x[30:32]), cu(t[30:32]), scale=cu(scale[30:32]), cfg=True)

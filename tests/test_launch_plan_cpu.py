@@ -3,7 +3,8 @@
 The header is host-only C++: a stand-alone driver (tests/launch_plan_driver.cpp) that includes nothing else of the project is compiled
 and run as a child process, and every field of plan_trunk, rows_ntb, plan_slices' count and slice_of's split are compared with the
 mirror, for every number of rows from 1 to 260, the frame counts at which a rule changes, guidance on and off, and every switch of the
-plan away from its default.  The GPU tests derive their case ids and path tables from the mirror; this is what ties the mirror to the
+plan away from its default; the two projections' plans (plan_embed_in, embed_next_ksn, plan_embed_out) at every feature width from 1
+to 512.  The GPU tests derive their case ids and path tables from the mirror; this is what ties the mirror to the
 code the engine runs."""
 import os
 import shutil
@@ -49,10 +50,15 @@ def mirror_line(k, rows, T):
     return out
 
 
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    path = str(tmp_path_factory.mktemp("plan") / "launch_plan_driver")
+    subprocess.run(["hipcc", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + CSRC, "-o", path, DRIVER], check=True)
+    return path
+
+
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc")
-def test_the_mirror_equals_the_header_over_the_sweep(tmp_path):
-    exe = str(tmp_path / "launch_plan_driver")
-    subprocess.run(["hipcc", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + CSRC, "-o", exe, DRIVER], check=True)
+def test_the_mirror_equals_the_header_over_the_sweep(exe):
     assert list(pm.KNOBS) == ["small_m", "small_ln", "small_ln_m", "small_fast", "precise", "fuse_qkv_attn", "fuse_tail", "tail_ntb",
                               "ln128_min_m", "trunk_groups", "num_layers", "nsplit", "dbg_stop"]          # PlanKnobs' order
     cases = [(name, pm.knobs(**over), rows, T) for name, over in KNOB_SETS.items() for T in FRAMES for rows in ROWS]
@@ -67,3 +73,64 @@ def test_the_mirror_equals_the_header_over_the_sweep(tmp_path):
         seen.add((got[0], got[32]))
     # the sweep reaches every path and every rows-GEMM tile height
     assert {p for p, _ in seen} == set(range(len(pm.PATHS))) and {n for _, n in seen} == {1, 2, 4}
+
+
+WIDTHS = range(1, 513)
+MODES = range(7)                    # DEpiEmbedOut<MODE>: 0 the model output alone, 1 .. 6 the loop steps (step_mode in mst_engine.hip)
+
+
+def embed_mirror_line(feats, T):
+    out = []
+    for precise in (0, 1):
+        for fast in (0, 1):
+            p = pm.plan_embed_in(feats, precise, fast)
+            out += [p[f] for f in pm.EMBED_IN_FIELDS]
+    for cfg in (0, 1):
+        for precise in (0, 1):
+            for fast in (0, 1):
+                out.append(pm.embed_next_ksn(feats, T, precise, fast))
+                for mode in MODES:
+                    for hi_lo in (0, 1):
+                        for custom in (0, 1):
+                            p = pm.plan_embed_out(feats, T, cfg, precise, fast, mode, hi_lo, custom)
+                            out += [p[f] for f in pm.EMBED_OUT_FIELDS]
+    return out
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc")
+def test_the_projection_plans_equal_their_mirror_at_every_width(exe):
+    """plan_embed_in / plan_embed_out / embed_next_ksn against the mirror for 1 .. 512 features, every frame count of FRAMES, guidance,
+    precise mode and embed_fast on and off, every step mode, split and plain streams, with and without a caller's weight -- and the
+    sweep reaches every instantiation the launchers switch over."""
+    cases = [(feats, T) for feats in WIDTHS for T in FRAMES]
+    text = "".join(f"{feats} {T}\n" for feats, T in cases)
+    r = subprocess.run([exe, "embed"], input=text, capture_output=True, text=True, check=True)
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(cases) == 512 * len(FRAMES)
+    n_in, n_out = len(pm.EMBED_IN_FIELDS), len(pm.EMBED_OUT_FIELDS)
+    ks_seen, out_seen, ksn_seen, ring_seen = set(), set(), set(), set()
+    for (feats, T), line in zip(cases, lines):
+        got, want = [int(v) for v in line.split()], embed_mirror_line(feats, T)
+        assert got == want, f"{feats} features, T {T}: header {got} != mirror {want}"
+        ins, outs = got[:4 * n_in], got[4 * n_in:]
+        ks_seen |= {(ins[i + 1], ins[i + 2]) for i in range(0, len(ins), n_in)}
+        per = 1 + 28 * n_out                        # one (cfg, precise, fast) block: embed_next_ksn, then 7 modes x hi_lo x custom
+        for b in range(0, len(outs), per):
+            for j, i in enumerate(range(b + 1, b + per, n_out)):
+                kernel, nbw, nx, staged, ksn, bf, xs = outs[i:i + n_out]
+                mode = j // 4
+                if pm.EMBED_KERNELS[kernel] == "latency":
+                    assert bf == xs == 0 and (not ksn or (staged and nx == 1 and ksn == outs[b]))
+                    out_seen.add((nbw, mode, nx, staged))
+                    if ksn:
+                        ksn_seen.add((nbw, mode, ksn))
+                else:
+                    assert nbw == staged == ksn == 0
+                    ring_seen.add((bf, nx, xs))
+    latency, ring = pm.EMBED_KERNELS.index("latency"), pm.EMBED_KERNELS.index("ring")
+    assert ks_seen == {(ks, k) for ks in range(3, 17) for k in (latency, ring)}                         # k_embed_in<3 .. 16>, and the ring
+    # k_embed_out<NBW, MODE, NX>: NX = 2 up to three blocks per wave; staged (T % 4 == 0, a step, NBW <= 3) and not
+    assert out_seen == {(nbw, mode, nx, st) for nbw in range(1, 5) for mode in MODES for nx in (1, 2) for st in (0, 1)
+                        if not (nbw == 4 and nx == 2) and not (st and (mode == 0 or nbw == 4))}
+    assert ksn_seen == {(nbw, mode, ksn) for nbw, ksn in ((2, 5), (2, 6), (3, 9)) for mode in range(1, 7)}
+    assert ring_seen == {(bf, nx, xs) for bf in (256, 384, 512) for nx in (1, 2) for xs in (1, 2) if not (bf == 512 and xs == 2)}
