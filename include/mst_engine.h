@@ -414,6 +414,16 @@ int mst_philox_normal(float* out_dev, int32_t batch, int32_t feats, int32_t fram
  *                       linear1.weight, .bias, linear2.weight, .bias, norm1.weight, .bias,
  *                       norm2.weight, .bias.  grads == NULL: no parameter gradients (frozen stack, input
  *                       gradient only).  rows / S / p_drop / seed must repeat the forward's.
+ * DYNAMIC RANGE of d_out (the same for mst_train_model_backward's d_out and mst_motion_encoder_backward's d_mu): ONE
+ * power of two per call brings max |d_out| into [16, 32), and every f16 operand of the backward pass lives behind it.
+ * The magnitude of the whole cotangent is therefore free (2^-30 is as accurate as 1), but its range INSIDE one call is
+ * f16's: a clip or token whose cotangent lies 2^-k below the call's largest entry meets f16 subnormals from k = 18 on and
+ * rounds to zero from about k = 29 on.  Supported: k <= 16 (R = 16: dL/d(h_in) of every clip within 1.5e-3 of float64; measured
+ * 3.7e-4 at k = 12, as at k = 0, and 1.4e-3 at k = 16, the edge); beyond, that clip's dL/d(h_in) degrades as f16's gradual
+ * underflow does, by about 2x per bit -- 2e-2 at 2^-20, 0.25 at 2^-24 -- while the parameter gradients, sums dominated by
+ * the large clips, keep their accuracy.  The fine-tune objective stays within 2^3.4 (chained steps and the text-to-motion
+ * batch in one pass; DESIGN section 5 has the table).  Cotangents of wider range belong in separate calls: the gradient
+ * buffers accumulate.
  * h_in, h_out, d_out, d_in: float32 [rows][S][512] (clip-major; the reference's [S, B, 512] permuted).
  * key_keep: NULL, or uint8 [rows][S] with 0 marking padding keys -- the inverse of the `src_key_padding_mask`
  * the frozen MotionEncoder passes to its own 8-layer stack (model/mdm_forstyledataset.py:90-124); every clip
