@@ -34,6 +34,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_encode.h"
 #include "mst_bvh.h"
 #include "mst_rotdec.h"
+#include "mst_eval.h"
 #include "mst_window.h"
 #include "mst_plan.h"
 
@@ -3722,6 +3723,107 @@ extern "C" int mst_rot_decode(const float* data, int64_t stride_batch, int64_t s
     p.local = local_rows;
     const size_t lds = route == kRotPosIk ? sizeof(float) * 2 * frames : 0;      // at most 32 KB: below the opt-in threshold
     hipLaunchKernelGGL(k_rot_decode, dim3(batch), dim3(kRotThreads), lds, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ evaluators and statistics (mst_eval.h)
+static bool eval_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int mst_eval_gemm(const float* a, const float* w, const float* bias, const float* add, float* c, int32_t m, int32_t n, int32_t k,
+                             int64_t lda, int64_t ldc, int64_t ldadd, int32_t mode, int32_t batch, int32_t frames_in, int32_t channels,
+                             int64_t ldx, int64_t stride_batch, const float* scale, const float* shift, int32_t leaky, void* stream) {
+    if (!a || !w || !c) return fail("mst_eval_gemm: null operand");
+    if (m < 1 || n < 1 || k < 1) return fail("mst_eval_gemm: M %d, N %d, K %d: each at least 1", m, n, k);
+    if ((m + EVAL_BM - 1) / EVAL_BM > 65535) return fail("mst_eval_gemm: M %d above %d rows", m, 65535 * EVAL_BM);
+    if (ldc < n) return fail("mst_eval_gemm: ldc %lld < N %d", (long long)ldc, n);
+    if (add && ldadd < n) return fail("mst_eval_gemm: ldadd %lld < N %d", (long long)ldadd, n);
+    if ((scale == nullptr) != (shift == nullptr)) return fail("mst_eval_gemm: scale and shift come together");
+    EvalGemmArgs p{};
+    p.a = a; p.w = w; p.bias = bias; p.add = add; p.scale = scale; p.shift = shift; p.c = c;
+    p.M = m; p.N = n; p.K = k; p.mode = mode; p.leaky = leaky != 0;
+    p.lda = lda; p.ldc = ldc; p.ldadd = ldadd; p.ldx = ldx; p.sb = stride_batch;
+    p.Tin = 1; p.Tout = 1; p.C = 1;
+    if (mode == kEvalPlain) {
+        if (lda < k) return fail("mst_eval_gemm: lda %lld < K %d", (long long)lda, k);
+        if (scale) return fail("mst_eval_gemm: the affine belongs to the conv prologues");
+    } else if (mode == kEvalConvRows || mode == kEvalConvSample) {
+        if (batch < 1 || frames_in < 2 || channels < 1) return fail("mst_eval_gemm: conv prologue: batch %d, frames %d (>= 2), channels %d", batch, frames_in, channels);
+        const int t_out = (frames_in - 2) / 2 + 1;
+        if (k != 4 * channels) return fail("mst_eval_gemm: conv prologue: K %d != 4 * channels %d", k, channels);
+        if ((int64_t)batch * t_out != m) return fail("mst_eval_gemm: conv prologue: M %d != batch %d * output frames %d", m, batch, t_out);
+        if (ldx < channels) return fail("mst_eval_gemm: conv prologue: %lld features a frame < channels %d", (long long)ldx, channels);
+        const int64_t need = mode == kEvalConvRows ? (int64_t)frames_in * ldx : ldx * frames_in;
+        if (stride_batch < need) return fail("mst_eval_gemm: conv prologue: batch stride %lld < %lld", (long long)stride_batch, (long long)need);
+        p.Tin = frames_in; p.Tout = t_out; p.C = channels;
+    } else {
+        return fail("mst_eval_gemm: mode %d is none of 0 (plain), 1 (conv over rows), 2 (conv over a sample)", mode);
+    }
+    hipLaunchKernelGGL(k_gemm_f32, dim3((n + EVAL_BN - 1) / EVAL_BN, (m + EVAL_BM - 1) / EVAL_BM), dim3(256), 0, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_eval_gru(const float* xproj, const float* w_hh, const float* b_hh, const float* hidden, const int32_t* steps_dev,
+                            int32_t batch, int32_t positions, int32_t width, int32_t max_steps, float* work, float* out, void* stream) {
+    if (!xproj || !w_hh || !b_hh || !hidden || !steps_dev || !work || !out) return fail("mst_eval_gru: null operand");
+    if (width < 64 || width % 64) return fail("mst_eval_gru: width %d is no multiple of 64", width);
+    if (batch < 1 || positions < 1) return fail("mst_eval_gru: batch %d, positions %d: each at least 1", batch, positions);
+    if (max_steps < 1 || max_steps > positions) return fail("mst_eval_gru: %d steps outside 1..%d positions", max_steps, positions);
+    if (!eval_aligned16(w_hh) || !eval_aligned16(work) || !eval_aligned16(out)) return fail("mst_eval_gru: w_hh, work and out are read 16 bytes at a time: unaligned pointer");
+    const int64_t tiles = (int64_t)(width / EVAL_GRU_UNITS) * ((batch + EVAL_GRU_CLIPS - 1) / EVAL_GRU_CLIPS);
+    if (tiles > 0x7fffffff) return fail("mst_eval_gru: batch %d too large", batch);
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t hn = (int64_t)batch * 2 * width;
+    EvalGruArgs p{xproj, w_hh, b_hh, steps_dev, batch, positions, width};
+    hipLaunchKernelGGL(k_gru_init, dim3((unsigned)((hn + 255) / 256)), dim3(256), 0, st, hidden, work, batch, width);
+    HIPCHECK(hipGetLastError());
+    for (int s = 0; s < max_steps; s++) {
+        const float* h_in = work + (s & 1) * hn;
+        float* h_out = s == max_steps - 1 ? out : work + ((s + 1) & 1) * hn;
+        hipLaunchKernelGGL(k_gru_step, dim3((unsigned)tiles, 2), dim3(256), 0, st, p, h_in, h_out, s);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int mst_eval_layernorm(const float* x, const float* gamma, const float* beta, float* y, int32_t rows, int32_t width, float eps,
+                                  int32_t leaky, void* stream) {
+    if (!x || !gamma || !beta || !y) return fail("mst_eval_layernorm: null operand");
+    if (rows < 1 || width < 1) return fail("mst_eval_layernorm: rows %d, width %d: each at least 1", rows, width);
+    hipLaunchKernelGGL(k_ln_leaky, dim3(rows), dim3(64), 0, (hipStream_t)stream, x, gamma, beta, y, width, eps, leaky != 0);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_eval_dist_rank(const float* e1, const float* e2, int32_t n1, int32_t n2, int32_t d, float* dist, int32_t* rank, void* stream) {
+    if (!e1 || !e2 || !dist) return fail("mst_eval_dist_rank: null operand");
+    if (n1 < 1 || n2 < 1) return fail("mst_eval_dist_rank: %d x %d rows: each at least 1", n1, n2);
+    if (d < 1 || d > EVAL_DIST_MAX_D) return fail("mst_eval_dist_rank: %d features outside 1..%d", d, EVAL_DIST_MAX_D);
+    if (rank && n1 != n2) return fail("mst_eval_dist_rank: the rank of the diagonal needs a square matrix, got %d x %d", n1, n2);
+    hipLaunchKernelGGL(k_dist_rank, dim3(n1), dim3(256), sizeof(float) * d, (hipStream_t)stream, e1, e2, n1, n2, d, dist, rank);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_eval_cov(const float* a, int32_t n, int32_t d, double* mean, double* cov, void* stream) {
+    if (!a || !mean) return fail("mst_eval_cov: null operand");
+    if (d < 1 || d > 16 * 65535) return fail("mst_eval_cov: %d features outside 1..%d", d, 16 * 65535);
+    if (n < 1 || (cov && n < 2)) return fail("mst_eval_cov: %d rows: the covariance needs at least 2", n);
+    hipLaunchKernelGGL(k_col_mean_f64, dim3((d + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, n, d, mean);
+    HIPCHECK(hipGetLastError());
+    if (cov) {
+        hipLaunchKernelGGL(k_cov_f64, dim3((d + 15) / 16, (d + 15) / 16), dim3(256), 0, (hipStream_t)stream, a, mean, n, d, cov);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int mst_eval_pair_norms(const float* a, const float* b, const int32_t* ia, const int32_t* ib, int32_t pairs, int32_t na, int32_t nb,
+                                   int32_t d, float* out, void* stream) {
+    if (!a || !b || !ia || !ib || !out) return fail("mst_eval_pair_norms: null operand");
+    if (pairs < 1 || na < 1 || nb < 1 || d < 1) return fail("mst_eval_pair_norms: pairs %d, rows %d / %d, features %d: each at least 1", pairs, na, nb, d);
+    hipLaunchKernelGGL(k_pair_norms, dim3((pairs + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, b, ia, ib, pairs, na, nb, d, out);
     HIPCHECK(hipGetLastError());
     return 0;
 }

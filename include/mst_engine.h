@@ -724,6 +724,51 @@ int mst_rot_decode_max_joints(void);
  * at the cap of 4096, what the windowed loops return.  -1 for joints outside 2 .. mst_rot_decode_max_joints. */
 int mst_rot_decode_max_frames(int32_t joints);
 
+/* -------------------------------------------------------------------------------------------
+ * The T2M evaluators (data_loaders/humanml/networks/modules.py: MovementConvEncoder, MotionEncoderBiGRUCo, TextEncoderBiGRUCo) and the
+ * statistics of data_loaders/humanml/utils/metrics.py, as building blocks: mst_amd.data_loaders.evaluator_wrapper and mst_amd.utils.metrics
+ * chain them.  Everything is fp32 -- operands, accumulation (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain, two chains an output), hidden
+ * state, expf / tanhf -- and the covariance double: an evaluator is the instrument the sampler is measured with.  No atomics: every
+ * result is a fixed-order sum, so a row does not depend on what else is in the batch.  All pointers are device pointers; every launch
+ * goes to `stream`; nothing is allocated and nothing synchronises.
+ *
+ * mst_eval_gemm: c[m][n] = act(sum_k A[m][k] w[n][k] + bias[n] + add[m][n]); bias and add optional, act LeakyReLU(0.2) when leaky.
+ * Any M, N, K >= 1.  mode 0: A[m][k] = a[m * lda + k].  mode 1, Conv1d(channels, N, 4, 2, 1) over rows a[b][frame][0 .. ldx): M =
+ * batch * T_out, T_out = (frames_in - 2) / 2 + 1, K = 4 * channels, k = tap * channels + channel (the weight laid out [N][4][channels]),
+ * output frame t reads frames 2 t - 1 + tap, frames outside the clip are zero; channels <= ldx drops trailing features.  mode 2: the same
+ * over a sample a[b][feature][0][frame] (ldx features).  stride_batch: elements between clips.  scale / shift [channels], both or neither,
+ * modes 1 and 2: every value read becomes x * scale + shift (the padding stays zero).
+ *
+ * mst_eval_gru: torch's bidirectional one-layer GRU over packed sequences, final hidden states only.  xproj [batch][positions][2][3][width]
+ * holds W_ih x + b_ih (gates r, z, n); w_hh [2][3 width][width], b_hh [2][3 width], hidden [2][1][width] the initial state, broadcast.
+ * Clip b takes part in steps 0 .. steps_dev[b] - 1 (clamped into 0 .. positions); the forward direction reads position s, the backward
+ * one steps[b] - 1 - s; a finished clip's state is carried.  max_steps (host): the number of step launches, the largest steps[b].
+ * work: 2 * batch * 2 * width floats; out [batch][2][width]: gru_last, forward then backward.  width a multiple of 64.
+ *
+ * mst_eval_layernorm: y = LeakyReLU?((x - mean) / sqrt(var + eps) * gamma + beta) per row, two-pass, biased variance.
+ *
+ * mst_eval_dist_rank: dist[i][j] = sqrt(max(-2 e1[i].e2[j] + |e1[i]|^2 + |e2[j]|^2, 0)) in fp32 (the reference's expansion; it yields
+ * NaN where rounding makes the radicand negative, this 0).  rank (optional, n1 == n2): per row the number of entries strictly below the
+ * diagonal one -- calculate_R_precision's top-k is rank < k.  d <= 8192.
+ *
+ * mst_eval_cov: mean[d] and, when cov is given (n >= 2), the (n - 1)-normalised covariance [d][d] of fp32 rows a[n][d], in double, the
+ * mean subtracted before the products (np.cov(rowvar=False)).
+ *
+ * mst_eval_pair_norms: out[k] = |a[ia[k]] - b[ib[k]]|, summed in fp32; an index outside its matrix gives NaN.
+ * ----------------------------------------------------------------------------------------- */
+int mst_eval_gemm(const float* a_dev, const float* w_dev, const float* bias_dev, const float* add_dev, float* c_dev, int32_t m, int32_t n,
+                  int32_t k, int64_t lda, int64_t ldc, int64_t ldadd, int32_t mode, int32_t batch, int32_t frames_in, int32_t channels,
+                  int64_t ldx, int64_t stride_batch, const float* scale_dev, const float* shift_dev, int32_t leaky, void* stream);
+int mst_eval_gru(const float* xproj_dev, const float* w_hh_dev, const float* b_hh_dev, const float* hidden_dev, const int32_t* steps_dev,
+                 int32_t batch, int32_t positions, int32_t width, int32_t max_steps, float* work_dev, float* out_dev, void* stream);
+int mst_eval_layernorm(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* y_dev, int32_t rows, int32_t width,
+                       float eps, int32_t leaky, void* stream);
+int mst_eval_dist_rank(const float* e1_dev, const float* e2_dev, int32_t n1, int32_t n2, int32_t d, float* dist_dev, int32_t* rank_dev,
+                       void* stream);
+int mst_eval_cov(const float* a_dev, int32_t n, int32_t d, double* mean_dev, double* cov_dev, void* stream);
+int mst_eval_pair_norms(const float* a_dev, const float* b_dev, const int32_t* ia_dev, const int32_t* ib_dev, int32_t pairs, int32_t na,
+                        int32_t nb, int32_t d, float* out_dev, void* stream);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
