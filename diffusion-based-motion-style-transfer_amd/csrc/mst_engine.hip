@@ -34,6 +34,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_encode.h"
 #include "mst_bvh.h"
 #include "mst_rotdec.h"
+#include "mst_jguide.h"
 #include "mst_eval.h"
 #include "mst_window.h"
 #include "mst_plan.h"
@@ -3223,6 +3224,36 @@ extern "C" int mst_recover_from_ric(const float* sample, const float* mean, cons
     if (sizeof(float) * 5 * frames > 64 * 1024) CHECK(ensure_dyn_lds((const void*)k_recover_from_ric, (int)sizeof(float) * 5 * max_frames));
     hipLaunchKernelGGL(k_recover_from_ric, dim3(batch), dim3(256), sizeof(float) * 5 * frames, (hipStream_t)stream, sample, mean, stdv,
                        feats, frames, joints, out);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// Joint-space guidance (mst_jguide.h): logp and d logp / d x0 in one launch.  k_joint_guide keeps 32 bytes a frame in dynamic LDS (three
+// double rows, two fp32 rows) beside the scans' wave totals; the bound stays inside the 64 KB a launch gets without an opt-in.
+extern "C" int mst_joint_guide_max_frames(void) {
+    int dev = 0, lds = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        fail("mst_joint_guide_max_frames: the device's shared memory per block cannot be read");
+        return -1;
+    }
+    const int n = (lds - 128) / kJgFrameBytes;
+    return n < kJgMaxFrames ? n : kJgMaxFrames;
+}
+extern "C" int mst_joint_guide(const float* x0, const float* mean, const float* stdv, const float* target, const float* weight,
+                               const float* scale, const int32_t* lengths, int32_t batch, int32_t feats, int32_t frames, int32_t joints,
+                               float* logp, float* grad, float* positions, void* stream) {
+    if (!x0 || !mean || !stdv || !target || !weight || !scale || !logp || !grad || batch < 1 || frames < 1 || joints < 1)
+        return fail("mst_joint_guide: bad arguments");
+    if (feats < 4 + 3 * (joints - 1)) return fail("mst_joint_guide: %d features cannot hold %d joints", feats, joints);
+    const int max_frames = mst_joint_guide_max_frames();
+    if (max_frames < 0) return 1;
+    if (frames > max_frames)
+        return fail("mst_joint_guide: frames %d > %d (mst_joint_guide_max_frames: 32 bytes a frame in LDS)", frames, max_frames);
+    if ((long long)feats * frames > 0x7fffffffLL || (long long)frames * joints * 3 > 0x7fffffffLL)
+        return fail("mst_joint_guide: a clip of %d x %d features and %d joints does not fit 32-bit offsets", feats, frames, joints);
+    JGuideArgs a{x0, mean, stdv, target, weight, scale, lengths, feats, frames, joints, logp, grad, positions};
+    hipLaunchKernelGGL(k_joint_guide, dim3(batch), dim3(kJgThreads), (size_t)kJgFrameBytes * frames, (hipStream_t)stream, a);
     HIPCHECK(hipGetLastError());
     return 0;
 }

@@ -315,6 +315,22 @@ class GaussianDiffusion:
         out["mean"], _, _ = self.q_posterior_mean_variance(x_start=out["pred_xstart"], x_t=x, t=t)
         return out
 
+    def condition_mean_with_grad(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """mean + variance * cond_fn(x, t, p_mean_var) (reference :469-482), torch ops on any device: the cond_fn sees the step's own
+        p_mean_var, whose pred_xstart is in the graph of x, and the UNSCALED t.  p_sample_with_grad does the same inside the step kernel."""
+        gradient = cond_fn(x, t, p_mean_var, **(model_kwargs or {}))
+        return p_mean_var["mean"].float() + p_mean_var["variance"] * gradient.float()
+
+    def condition_score_with_grad(self, cond_fn, p_mean_var, x, t, model_kwargs=None):
+        """condition_score with the with-grad cond_fn signature (reference :508-530), torch ops on any device."""
+        alpha_bar = _extract_into_tensor(self.alphas_cumprod, t, x.shape)
+        eps = self._predict_eps_from_xstart(x, t, p_mean_var["pred_xstart"])
+        eps = eps - (1 - alpha_bar).sqrt() * cond_fn(x, t, p_mean_var, **(model_kwargs or {}))
+        out = p_mean_var.copy()
+        out["pred_xstart"] = self._predict_xstart_from_eps(x, t, eps)
+        out["mean"], _, _ = self.q_posterior_mean_variance(x_start=out["pred_xstart"], x_t=x, t=t)
+        return out
+
     def _fused_step(self, sampler, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, const_noise, eta=0.0):
         if sampler == _eng.SAMPLER_DDIM_REVERSE and (cond_fn is not None or denoised_fn is not None):
             raise NotImplementedError("ddim_reverse_sample: cond_fn / denoised_fn are not built for the reverse step (the reference's "
@@ -384,7 +400,7 @@ class GaussianDiffusion:
         return self._fused_step(_eng.SAMPLER_DDIM_REVERSE, model, x, t, clip_denoised, denoised_fn, None, model_kwargs, False, 0.0)
 
     # -- autograd-carrying variants (fine-tune loss): x0-hat may stay in the graph ---------------
-    def _grad_step(self, ddim, model, x, t, clip_denoised, model_kwargs, pred_xstart_in_graph, const_noise=False, eta=0.0):
+    def _grad_step(self, ddim, model, x, t, clip_denoised, model_kwargs, pred_xstart_in_graph, const_noise=False, eta=0.0, cond_fn=None):
         """One `*_with_grad` step (reference inpainting_gaussian_diffusion.py:66-123 / :179-239): the model call is the native
         training node, everything behind it -- inpainting blend, x0-hat, posterior mean or DDIM update, masked noise -- ONE
         autograd node over the fused step kernel (fused_ops.FusedStepFn) instead of ~20 elementwise torch ops.  As in the
@@ -395,6 +411,8 @@ class GaussianDiffusion:
         if self.model_mean_type != ModelMeanType.START_X:
             raise NotImplementedError("this model family predicts x_start (utils/model_util.py:172)")
         assert t.shape == (x.shape[0],)
+        if cond_fn is not None:
+            return self._guided_grad_step(ddim, model, x, t, clip_denoised, cond_fn, model_kwargs, pred_xstart_in_graph, const_noise, eta)
         with th.enable_grad():
             x = x.detach()
             out = self._model_output(model, x, t, model_kwargs)
@@ -410,15 +428,72 @@ class GaussianDiffusion:
                                              _eng.SAMPLER_DDIM if ddim else _eng.SAMPLER_DDPM, eta, nmask is not None, clip_denoised)
         return {"sample": sample, "pred_xstart": pred if pred_xstart_in_graph else pred.detach()}
 
+    def _step_table(self, name, arr, t, shape):
+        """_extract_into_tensor from a device copy of the table made once per device (a fresh upload per step is a blocking copy)."""
+        cache = self.__dict__.setdefault("_step_tables", {})
+        key = (name, t.device)
+        tab = cache.get(key)
+        if tab is None:
+            tab = cache[key] = th.from_numpy(np.asarray(arr)).to(device=t.device).float()
+        return tab[t].view(-1, *([1] * (len(shape) - 1))).expand(shape)
+
+    def _guided_grad_step(self, ddim, model, x, t, clip_denoised, cond_fn, model_kwargs, pred_xstart_in_graph, const_noise, eta):
+        """One `*_with_grad` step with a cond_fn (reference inpainting_gaussian_diffusion.py:66-123 / :179-239 with
+        condition_mean_with_grad / condition_score_with_grad, gaussian_diffusion.py:469-482 / :508-530).  x requires grad; the model
+        call is the native training node, created so that its backward is the input-gradient-only pass; x0-hat behind the inpainting
+        blend and the clamp is FusedStepFn's output; cond_fn(x, t, p_mean_var, **model_kwargs) -- the unscaled t, as in the
+        reference -- returns grad log p(y | x_t), which the guided step kernel applies (MST_GUIDE_GRADIENT: condition_mean for the
+        ancestral step, condition_score for DDIM at any eta).  The sample is a plain tensor (the loops cut it from the graph anyway);
+        pred_xstart is the UNGUIDED x0-hat, detached."""
+        from .fused_ops import FusedStepFn
+        from ..model.native_stack import input_grad_only
+        who = "ddim_sample_with_grad" if ddim else "p_sample_with_grad"
+        if pred_xstart_in_graph:
+            raise NotImplementedError(f"{who}: cond_fn together with pred_xstart_in_graph -- the cond_fn's backward releases the node's "
+                                      "activation tape, so the returned x0-hat could not be differentiated again")
+        from .guidance import TargetGuide
+        if isinstance(cond_fn, TargetGuide):
+            raise ValueError(f"{who}: a TargetGuide is a cond_fn of (x, t) on the noisy sample; use it without cond_fn_with_grad")
+        if _unwrap(model)[1] is not None:
+            raise NotImplementedError(f"{who}: a with-grad cond_fn on a ClassifierFreeSampleModel (two native nodes per step under one "
+                                      "guidance scale) is not built; guide the unwrapped model")
+        assert x.is_cuda, f"{who} with a cond_fn: the guided step runs on the GPU only (there is no CPU fallback)"
+        sampler = _eng.SAMPLER_DDIM if ddim else _eng.SAMPLER_DDPM
+        with th.enable_grad():
+            x = x.detach().requires_grad_()
+            with input_grad_only():
+                out = self._model_output(model, x, t, model_kwargs)
+        noise = self._draw(x, const_noise).contiguous().float()
+        mask, motion = self._inpaint_pair(model_kwargs)
+        if mask is not None:
+            assert out.shape == mask.shape == motion.shape
+        nmask = self._noise_mask(model_kwargs)
+        sch = self._schedule(x.device)
+        xd = x.detach().contiguous().float()
+        step_mask = mask if mask is not None else nmask
+        var, logvar = self._variance_tables()
+        with th.enable_grad():
+            _, pred = FusedStepFn.apply(out, xd, t, noise, step_mask, motion, sch, sampler, eta, nmask is not None, clip_denoised)
+            mean = (self._step_table("posterior_mean_coef1", self.posterior_mean_coef1, t, x.shape) * pred
+                    + self._step_table("posterior_mean_coef2", self.posterior_mean_coef2, t, x.shape) * x)
+            p_mean_var = {"mean": mean, "variance": self._step_table(("variance", self.model_var_type), var, t, x.shape),
+                          "log_variance": self._step_table(("log_variance", self.model_var_type), logvar, t, x.shape),
+                          "pred_xstart": pred}
+            gradient = cond_fn(x, t, p_mean_var, **(model_kwargs or {}))
+        assert gradient.shape == x.shape, "cond_fn must return a gradient of x's shape"
+        sample, _ = sch.step_guided(out.detach(), xd, t, noise, _eng.guide_args(xd, grad=gradient.detach().float()), sampler, eta,
+                                    mask=step_mask, motion=motion, mask_noise=nmask is not None, clip_denoised=clip_denoised)
+        return {"sample": sample, "pred_xstart": pred.detach()}
+
     def p_sample_with_grad(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                            pred_xstart_in_graph=False, const_noise=False):
-        assert cond_fn is None and denoised_fn is None
-        return self._grad_step(False, model, x, t, clip_denoised, model_kwargs, pred_xstart_in_graph, const_noise)
+        assert denoised_fn is None, "p_sample_with_grad: denoised_fn is not supported"
+        return self._grad_step(False, model, x, t, clip_denoised, model_kwargs, pred_xstart_in_graph, const_noise, cond_fn=cond_fn)
 
     def ddim_sample_with_grad(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                               eta=0.0, pred_xstart_in_graph=False):
-        assert cond_fn is None and denoised_fn is None
-        return self._grad_step(True, model, x, t, clip_denoised, model_kwargs, pred_xstart_in_graph, False, eta)
+        assert denoised_fn is None, "ddim_sample_with_grad: denoised_fn is not supported"
+        return self._grad_step(True, model, x, t, clip_denoised, model_kwargs, pred_xstart_in_graph, False, eta, cond_fn=cond_fn)
 
     # ------------------------------------------------------------------------------ loops
     @staticmethod
@@ -543,7 +618,7 @@ class GaussianDiffusion:
             with chain:
                 device, img, indices = self._loop_setup(model, shape, noise, device, skip_timesteps, init_image, stop_timesteps, model_kwargs)
             yield from self._grad_steps(ddim, model, img, indices, shape, device, progress, clip_denoised, model_kwargs, eta,
-                                        const_noise, pred_xstart_in_graph, chain)
+                                        const_noise, pred_xstart_in_graph, chain, cond_fn=cond_fn)
             return
         device, img, indices = self._loop_setup(model, shape, noise, device, skip_timesteps, init_image, stop_timesteps, model_kwargs)
         yield from self._steps_from(_eng.SAMPLER_DDIM if ddim else _eng.SAMPLER_DDPM, model, device, img, indices, clip_denoised,
@@ -592,8 +667,9 @@ class GaussianDiffusion:
         return t
 
     def _grad_steps(self, ddim, model, img, indices, shape, device, progress, clip_denoised, model_kwargs, eta, const_noise,
-                    pred_xstart_in_graph, chain):
-        """The *_with_grad loop (reference gaussian_diffusion.py:775-794 with cond_fn_with_grad): every step's x0-hat stays in the graph."""
+                    pred_xstart_in_graph, chain, cond_fn=None):
+        """The *_with_grad loop (reference gaussian_diffusion.py:775-794 with cond_fn_with_grad): every step's x0-hat stays in the graph.
+        A cond_fn is the with-grad kind, cond_fn(x, t, p_mean_var, **model_kwargs), and guides every step."""
         if progress:
             from tqdm.auto import tqdm
             indices = tqdm(indices)
@@ -601,9 +677,10 @@ class GaussianDiffusion:
             with chain:
                 t = self._const_timesteps(int(i), shape[0], device)
                 with th.no_grad():
-                    out = (self.ddim_sample_with_grad(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta,
+                    out = (self.ddim_sample_with_grad(model, img, t, clip_denoised=clip_denoised, cond_fn=cond_fn,
+                                                      model_kwargs=model_kwargs, eta=eta,
                                                       pred_xstart_in_graph=pred_xstart_in_graph) if ddim else
-                           self.p_sample_with_grad(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs,
+                           self.p_sample_with_grad(model, img, t, clip_denoised=clip_denoised, cond_fn=cond_fn, model_kwargs=model_kwargs,
                                                    const_noise=const_noise, pred_xstart_in_graph=pred_xstart_in_graph))
             yield out
             img = out["sample"]

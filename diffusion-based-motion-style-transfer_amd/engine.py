@@ -273,6 +273,48 @@ def guide_args(x, grad=None, target=None, mask=None, weight=None, follow_schedul
     return g, keep
 
 
+def joint_guide_max_frames():
+    """Longest clip `joint_guide` takes on the current device (mst_joint_guide_max_frames)."""
+    n = int(N.lib().mst_joint_guide_max_frames())
+    if n < 0:
+        N.check(1)
+    return n
+
+
+def joint_guide(x0, mean, std, joints, target, weight, scale, lengths=None, want_positions=False):
+    """(logp [B], grad [B,F,1,T]) -- with want_positions also the positions [B,T,joints,3] -- of the joint-space likelihood
+    logp = -1/2 scale sum_{t < len} weight (recover_from_ric(x0 * std + mean, joints) - target)^2 and its gradient with respect to the
+    normalised rows x0 [B,F,1,T] (mst_joint_guide, csrc/mst_jguide.h: one launch, forward and reverse pass).  target, weight:
+    [B,T,joints,3]; scale: one value or one per clip; lengths: [B] or None.  Everything float32 on x0's GPU; there is no other
+    implementation, a CPU x0 raises."""
+    _need_gpu(x0, "joint_guide: x0")
+    dev = x0.device
+    if x0.dim() != 4 or x0.shape[2] != 1:
+        raise ValueError(f"joint_guide: x0 must be [B, F, 1, T], got {tuple(x0.shape)}")
+    B, F, _, T = x0.shape
+    J = int(joints)
+    if J < 1 or F < 4 + 3 * (J - 1):
+        raise ValueError(f"joint_guide: {F} features cannot hold {J} joints (4 + 3 (J - 1) position channels)")
+    x0 = _f32c(x0, dev, "x0")
+    mean, std = _f32c(mean, dev, "mean").reshape(-1), _f32c(std, dev, "std").reshape(-1)
+    if mean.numel() != F or std.numel() != F:
+        raise ValueError(f"joint_guide: mean / std hold {mean.numel()} / {std.numel()} values for {F} features")
+    target = _operand(target, (B, T, J, 3), "joint_guide: target", RULE_EQUAL, dev)
+    weight = _operand(weight, (B, T, J, 3), "joint_guide: weight", RULE_EQUAL, dev)
+    scale = _operand(scale, (B,), "joint_guide: scale", RULE_SCALE, dev)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        if lengths.numel() != B:
+            raise ValueError(f"joint_guide: {lengths.numel()} lengths for {B} clips")
+    logp = torch.empty(B, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(x0)
+    pos = torch.empty(B, T, J, 3, dtype=torch.float32, device=dev) if want_positions else None
+    with torch.cuda.device(dev):      # the entry point asks the current device for its LDS size (no device argument in the ABI)
+        N.check(N.lib().mst_joint_guide(N.ptr(x0), N.ptr(mean), N.ptr(std), N.ptr(target), N.ptr(weight), N.ptr(scale), N.ptr(lengths),
+                                        B, F, T, J, N.ptr(logp), N.ptr(grad), N.ptr(pos), N.stream_ptr(dev)))
+    return (logp, grad, pos) if want_positions else (logp, grad)
+
+
 def plan_style_segments(styles, S, tile_rows):
     """Host-only (no GPU): the {row0, row_lo, row_hi, slot} segments the style-aware kernels run for rows of clips with these slots."""
     s = np.ascontiguousarray(np.asarray(styles, dtype=np.int32).reshape(-1))

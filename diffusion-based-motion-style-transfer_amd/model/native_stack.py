@@ -403,6 +403,23 @@ class ChainedCalls:
             self.dbuf = None
 
 
+_INPUT_ONLY = 0
+
+
+@contextlib.contextmanager
+def input_grad_only():
+    """Native denoiser nodes created inside this block return dL/dx alone, whatever `requires_grad` the parameters carry: their backward
+    is mst_train_model_backward with grads = NULL -- no weight-gradient kernel, no gradient sink, no parameter's `.grad` touched.
+    The with-grad guided samplers run the model in it: a cond_fn asks for the gradient with respect to x_t of a model loaded with
+    trainable parameters."""
+    global _INPUT_ONLY
+    _INPUT_ONLY += 1
+    try:
+        yield
+    finally:
+        _INPUT_ONLY -= 1
+
+
 class DenoiserTrainFn(torch.autograd.Function):
     """The WHOLE denoiser call as one node: conditioning token, pose embedding, positional-encoding dropout, the trainable
     stack and the output projection (mst_train_model_forward / _backward).  Used when the module conditions on text (every
@@ -414,7 +431,8 @@ class DenoiserTrainFn(torch.autograd.Function):
         cond_drop = host.__dict__.pop("_mst_cond_drop", None)      # mask_cond's Bernoulli mask, applied inside the projection (_native_train_call)
         block = ChainedCalls.current
         chain = block if _CHAIN_ON() else None
-        if chain is not None and not (B == 1 and not ctx.needs_input_grad[0] and any(ctx.needs_input_grad[6:])):
+        ctx.want_params = any(ctx.needs_input_grad[6:]) and not _INPUT_ONLY
+        if chain is not None and not (B == 1 and not ctx.needs_input_grad[0] and ctx.want_params):
             chain = None
         seed = _draw_seed(max(p_drop, p_pe))
         ctx.p_drop, ctx.p_pe, ctx.host, ctx.params, ctx.chain = p_drop, p_pe, host, params, None
@@ -442,7 +460,7 @@ class DenoiserTrainFn(torch.autograd.Function):
             if block is not None and block.side is not None:
                 out.record_stream(block.side)
         ctx.tape, ctx.seed = tape, seed
-        if any(ctx.needs_input_grad[6:]):
+        if ctx.want_params:
             _sink_of(host, params).open_nodes += 1
         return out
 
@@ -454,7 +472,7 @@ class DenoiserTrainFn(torch.autograd.Function):
         need_in = ctx.needs_input_grad[0]
         tape = _take_tape(ctx)            # raises on a second backward BEFORE the sink is touched
         try:
-            views = _sink_views(ctx, any(ctx.needs_input_grad[6:]), grad_out.device)
+            views = _sink_views(ctx, ctx.want_params, grad_out.device)      # (input_grad_only: None, the backward with grads = NULL)
             d_x = ctx.eng.train_model_backward(tape, grad_out.contiguous(), ctx.p_drop, ctx.p_pe, ctx.seed, views,
                                                need_input_grad=need_in)
             _node_done(ctx, views is not None)

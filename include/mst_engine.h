@@ -520,6 +520,31 @@ int mst_recover_from_ric(const float* sample_dev, const float* mean_dev, const f
 int mst_recover_max_frames(void);
 
 /* -------------------------------------------------------------------------------------------
+ * Joint-space guidance, one launch, one workgroup per clip: the log-likelihood of world-space joint positions of a denoised clip and
+ * its gradient.  This is what a with-grad cond_fn (diffusion/gaussian_diffusion.py:469-482, :508-530; called from
+ * diffusion/inpainting_gaussian_diffusion.py:66-123, :179-239) evaluates on p_mean_var["pred_xstart"] when the constraint is on joints:
+ *     p       = recover_from_ric(x0 * std + mean, joints)       data_loaders/humanml/scripts/motion_process.py:389-410, :444-461
+ *     logp[b] = -1/2 scale[b] sum_{t < len_b, j, c} weight (p - target)^2
+ *     grad    = d logp / d x0   (normalised features: the std[f] factor is included)
+ * x0_dev, grad_dev: [batch][feats][1][frames] float32, the samplers' layout; mean_dev / std_dev: [feats]; feats >= 4 + 3 (joints - 1):
+ * the 263-feature HumanML row at 22 joints and the 9 J + 1 position-rotation row both qualify.  target_dev, weight_dev:
+ * [batch][frames][joints][3], weight >= 0 per axis, 0 = unconstrained (the target is then not used).  scale_dev: [batch].
+ * lengths_dev: [batch] int32, 0 <= len <= frames, or NULL; the kernel clamps the values into that range.  positions_dev:
+ * [batch][frames][joints][3] or NULL.  The yaw quaternion is (cos a, 0, sin a, 0) with the full angle, as the reference has it.
+ * The reverse pass is written by hand in the same launch; its three suffix sums and the forward map's three prefix sums are workgroup
+ * scans in double with a fixed order, no atomics: a clip's result is the same bits alone, anywhere in a batch and from run to run.
+ * Channels the map does not read and frames at or past a clip's length receive exact zeros, and what such frames hold changes no output.
+ * Refused here: null operands, batch / frames / joints < 1, feats too small for the joints, frames above mst_joint_guide_max_frames.
+ * ----------------------------------------------------------------------------------------- */
+int mst_joint_guide(const float* x0_dev, const float* mean_dev, const float* std_dev, const float* target_dev, const float* weight_dev,
+                    const float* scale_dev, const int32_t* lengths_dev, int32_t batch, int32_t feats, int32_t frames, int32_t joints,
+                    float* logp_dev, float* grad_dev, float* positions_dev, void* stream);
+/* Longest clip mst_joint_guide takes on the current device: the kernel keeps 32 bytes a frame in dynamic LDS (three double rows, two
+ * fp32 rows), so this is min(2040, (shared memory per block - 128) / 32) -- above the 223 frames of the training node; longer clips
+ * are refused on the host.  -1 when the device cannot be asked. */
+int mst_joint_guide_max_frames(void);
+
+/* -------------------------------------------------------------------------------------------
  * Foot-skate cleanup of joint clips, one launch, one workgroup per clip: the reference's remove_fs
  * (data_loaders/humanml/common/bvh_utils.py:1685-1809) with get_foot_contact_by_vel_acc (:1591-1639, use_vel3 = 0; thr is its
  * 0.003, use_window its window refinement), get_foot_contact_by_vel3 (:1642-1682, use_vel3 != 0) and Butterworth (:1872-1916;
