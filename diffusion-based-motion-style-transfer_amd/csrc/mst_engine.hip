@@ -38,6 +38,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_eval.h"
 #include "mst_window.h"
 #include "mst_plan.h"
+#include "mst_vb.h"
 
 using namespace mst;
 
@@ -2410,6 +2411,76 @@ extern "C" int mst_philox_normal(float* out, int32_t batch, int32_t feats, int32
     int n = feats * ((frames + 3) / 4);
     hipLaunchKernelGGL(k_philox_normal, dim3((n + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream, out, feats, frames,
                        (unsigned long long)seed, (unsigned)step);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ variational bound (mst_vb.h)
+// A draw needs the clip's layout (the counter is (frame quad, feature, clip, t)); a buffer does not.
+static int vb_draw_check(const char* who, int64_t per_clip, int32_t feats, int32_t frames) {
+    if (feats < 1 || frames < 1) return fail("%s: a drawn noise (noise_dev NULL) needs feats and frames (got %d, %d)", who, feats, frames);
+    if ((int64_t)feats * frames != per_clip)
+        return fail("%s: feats %d x frames %d is not per_clip %lld", who, feats, frames, (long long)per_clip);
+    if ((int64_t)feats * ((frames + 3) / 4) > 0x7fffffffLL) return fail("%s: feats x frames too large for a drawn noise", who);
+    return 0;
+}
+
+// q_sample on rows (clip[r], t[r]) (gaussian_diffusion.py:267-285 as calc_bpd_loop calls it, :1573-1574).
+extern "C" int mst_vb_diffuse(const mst_schedule* s, const float* x0, const float* noise, const float* mask, const int64_t* clip,
+                              const int64_t* t, int32_t rows, int64_t per_clip, int32_t feats, int32_t frames, uint64_t seed, float* out,
+                              void* stream) {
+    if (!s || !x0 || !clip || !t || !out) return fail("mst_vb_diffuse: null argument");
+    if (rows < 1 || per_clip < 1) return fail("mst_vb_diffuse: rows %d and per_clip %lld must be >= 1", rows, (long long)per_clip);
+    if (!noise) CHECK(vb_draw_check("mst_vb_diffuse", per_clip, feats, frames));
+    ON_DEVICE(s->device);
+    if (noise) {
+        int gx = (int)((per_clip + 255) / 256);
+        if (gx > 2048) gx = 2048;
+        hipLaunchKernelGGL(k_vb_diffuse, dim3(gx, rows), dim3(256), 0, (hipStream_t)stream, s->tab, s->n, x0, noise, mask,
+                           (const long long*)clip, (const long long*)t, (long long)per_clip, out);
+    } else {
+        int gx = (int)(((int64_t)feats * ((frames + 3) / 4) + 255) / 256);
+        if (gx > 2048) gx = 2048;
+        hipLaunchKernelGGL(k_vb_diffuse_draw, dim3(gx, rows), dim3(256), 0, (hipStream_t)stream, s->tab, s->n, x0, mask,
+                           (const long long*)clip, (const long long*)t, feats, frames, (unsigned long long)seed, out);
+    }
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// _vb_terms_bpd given the model output (gaussian_diffusion.py:1281-1314) plus the loop's two MSEs (:1586-1588), one workgroup per row.
+extern "C" int mst_vb_terms(const mst_schedule* s, const float* true_logvar, const float* x0, const float* x_t, const float* model_out,
+                            const float* noise, const float* mask, const float* motion, const int64_t* clip, const int64_t* t,
+                            int32_t rows, int64_t per_clip, int32_t feats, int32_t frames, uint64_t seed, int32_t mean_type,
+                            int32_t clip_denoised, float* out, float* xstart, void* stream) {
+    if (!s || !true_logvar || !x0 || !x_t || !model_out || !clip || !t || !out) return fail("mst_vb_terms: null argument");
+    if (rows < 1 || per_clip < 1) return fail("mst_vb_terms: rows %d and per_clip %lld must be >= 1", rows, (long long)per_clip);
+    if (mean_type < 0 || mean_type > 2) return fail("mst_vb_terms: bad mean type %d (0 = x_start, 1 = epsilon, 2 = previous x)", mean_type);
+    if ((mask != nullptr) != (motion != nullptr)) return fail("mst_vb_terms: the inpainting pair is mask AND motion, or neither");
+    if (!noise) CHECK(vb_draw_check("mst_vb_terms", per_clip, feats, frames));
+    ON_DEVICE(s->device);
+#define VB_LAUNCH(M_, D_)                                                                                                                \
+    hipLaunchKernelGGL((k_vb_terms<M_, D_>), dim3(rows), dim3(VB_THREADS), 0, (hipStream_t)stream, s->tab, true_logvar, s->n, x0, x_t,    \
+                       model_out, noise, mask, motion, (const long long*)clip, (const long long*)t, (long long)per_clip, feats, frames,   \
+                       (unsigned long long)seed, clip_denoised, out, xstart)
+    switch (mean_type) {
+        case 0: if (noise) VB_LAUNCH(0, false); else VB_LAUNCH(0, true); break;
+        case 1: if (noise) VB_LAUNCH(1, false); else VB_LAUNCH(1, true); break;
+        default: if (noise) VB_LAUNCH(2, false); else VB_LAUNCH(2, true); break;
+    }
+#undef VB_LAUNCH
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// _prior_bpd (gaussian_diffusion.py:1529-1545): the same reduction over x_start^2, one workgroup per clip.
+extern "C" int mst_vb_prior(const mst_schedule* s, const float* x0, int32_t batch, int64_t per_clip, float sqrt_ac_last, float log_1m_ac_last, float* out,
+                            void* stream) {
+    if (!s || !x0 || !out) return fail("mst_vb_prior: null argument");
+    if (batch < 1 || per_clip < 1) return fail("mst_vb_prior: batch %d and per_clip %lld must be >= 1", batch, (long long)per_clip);
+    ON_DEVICE(s->device);
+    hipLaunchKernelGGL(k_vb_prior, dim3(batch), dim3(VB_THREADS), 0, (hipStream_t)stream, x0, (long long)per_clip, sqrt_ac_last,
+                       log_1m_ac_last, out);
     HIPCHECK(hipGetLastError());
     return 0;
 }

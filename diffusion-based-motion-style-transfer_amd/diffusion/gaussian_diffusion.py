@@ -105,6 +105,43 @@ def _refuse_bank(model, what):
         raise RuntimeError(f"{what}: a StyleBank does not run under autograd; fine-tune each StyleDiffusion on its own")
 
 
+def vb_row_plan(n_clips, num_timesteps, rows=None):
+    """The (clip, timestep) rows of `calc_bpd_loop` as chunks [(clip indices, timestep indices)] of at most `rows` rows each: timestep
+    DESCENDING (the reference's visiting order, :1571) and, inside a timestep, clip ascending, so the concatenated results view as
+    [T, N] with row 0 = t = T - 1.  A chunk holds WHOLE timesteps of all N clips: `rows` is rounded down to a multiple of N, and refused
+    below N.  Default: max(N, 64 // N * N), the benchmark batch.  rows = N is the reference's loop structure."""
+    n, T = int(n_clips), int(num_timesteps)
+    if n < 1 or T < 1:
+        raise ValueError(f"vb_row_plan: {n} clips and {T} timesteps (both must be >= 1)")
+    rows = max(n, 64 // n * n) if rows is None else int(rows)
+    if rows < n:
+        raise ValueError(f"vb_row_plan: rows {rows} is below the {n} clips of one timestep")
+    per = rows // n
+    ts = list(range(T))[::-1]
+    return [([c for _ in ts[i:i + per] for c in range(n)], [t for t in ts[i:i + per] for _ in range(n)]) for i in range(0, T, per)]
+
+
+# entries of model_kwargs['y'] that hold one item per clip (data_loaders' collate, cfg_sampler, style_bank); everything else passes through
+VB_PER_CLIP = ("mask", "lengths", "text", "text_embed", "scale", "inpainting_mask", "inpainted_motion", "style")
+
+
+def vb_gather_kwargs(model_kwargs, clip, clip_dev, n_clips):
+    """model_kwargs for a batch of rows: every per-clip entry of y gathered by the rows' clip index -- tensors with leading dimension N by
+    index_select, lists (the `text` prompts) by index; scalars, flags and anything else as they are."""
+    y = (model_kwargs or {}).get('y')
+    if y is None:
+        return model_kwargs
+    g = {}
+    for k, v in y.items():
+        if k in VB_PER_CLIP:
+            if isinstance(v, th.Tensor) and v.dim() >= 1 and v.shape[0] == n_clips:
+                v = v.index_select(0, clip_dev.to(v.device))
+            elif isinstance(v, (list, tuple)) and len(v) == n_clips:
+                v = [v[i] for i in clip]
+        g[k] = v
+    return {**model_kwargs, 'y': g}
+
+
 class GaussianDiffusion:
     TABLES = ("betas", "alphas_cumprod", "alphas_cumprod_prev", "alphas_cumprod_next", "sqrt_alphas_cumprod",
               "sqrt_one_minus_alphas_cumprod", "log_one_minus_alphas_cumprod", "sqrt_recip_alphas_cumprod",
@@ -1136,6 +1173,86 @@ class GaussianDiffusion:
                 dump.append(out["pred_xstart"])
             final = out
         return dump if dump_all_xstart else final["sample"]
+
+    # ------------------------------------------------------------------------------ variational bound
+    def _vb_true_logvar(self, device):
+        """posterior_log_variance_clipped as a float32 device row: the TRUE posterior's log-variance (the schedule's own row is the
+        model's, which differs under FIXED_LARGE)."""
+        rows = self.__dict__.setdefault("_vb_logvar_rows", {})
+        key = th.device(device).index or 0
+        if key not in rows:
+            rows[key] = th.from_numpy(self.posterior_log_variance_clipped.astype(np.float32)).to(device)
+        return rows[key]
+
+    def _vb_rows(self, model, x_start, x_t, clip, t, noise, seed, clip_denoised, row_kwargs, pair, want_xstart):
+        """The model on the rows' x_t, then ONE launch for their terms: ([R, 4], x0-hat or None), `Schedule.vb_terms`."""
+        sch = self._schedule(x_start.device)
+        with th.no_grad():
+            out = self._model_output(model, x_t, t, row_kwargs)
+        mean_type = {ModelMeanType.START_X: 0, ModelMeanType.EPSILON: 1, ModelMeanType.PREVIOUS_X: 2}[self.model_mean_type]
+        return sch.vb_terms(self._vb_true_logvar(x_start.device), x_start, x_t, out, clip, t, noise=noise, seed=seed, mask=pair[0],
+                            motion=pair[1], clip_denoised=clip_denoised, mean_type=mean_type, want_xstart=want_xstart)
+
+    def _prior_bpd(self, x_start):
+        """The prior term of the bound in bits per dimension, [N] (reference :1529-1545): KL(q(x_T | x_0) || N(0, I)); one launch."""
+        return self._schedule(x_start.device).vb_prior(x_start, self.sqrt_alphas_cumprod[-1], self.log_one_minus_alphas_cumprod[-1])
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """One term of the bound in bits, {'output': [N], 'pred_xstart': x0-hat} (reference :1281-1314): the decoder NLL where t == 0,
+        KL(q(x_{t-1} | x_t, x_0) || p(x_{t-1} | x_t)) elsewhere.  `_model_output` plus one `vb_terms` launch on the rows (n, t[n]).
+        An evaluation, not an objective: the model runs under no_grad and nothing returned carries a graph (the reference's method is
+        differentiable torch code, used so only by training losses this code base does not have)."""
+        assert x_start.shape == x_t.shape and t.shape == (x_start.shape[0],)
+        clip = th.arange(x_start.shape[0], device=x_start.device)
+        # (the launch's eps MSE needs a noise operand that this signature does not have: x_t stands in, the column is not returned)
+        terms, pred = self._vb_rows(model, x_start, x_t, clip, t, x_t, 0, clip_denoised, model_kwargs or {},
+                                    self._inpaint_pair(model_kwargs), True)
+        return {"output": terms[:, 0], "pred_xstart": pred}
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, *, noise=None, seed=None, rows=None,
+                      progress=False):
+        """The whole variational bound in bits per dimension (reference :1547-1602): {'total_bpd': [N], 'prior_bpd': [N], 'vb': [N, T],
+        'xstart_mse': [N, T], 'mse': [N, T]}.  As in the reference, which appends while t descends, COLUMN 0 IS t = T - 1 and the last
+        column is t = 0.  Runs under no_grad.
+
+        The T timesteps are independent, so (clip, timestep) pairs are packed `rows` to a model call (`vb_row_plan`; default: whole
+        timesteps of all N clips up to 64 rows) instead of T calls of N clips; every per-clip entry of model_kwargs['y'] is gathered by
+        the rows' clip index.  noise: [T, N, F, 1, frames] indexed by t (what makes a run comparable with the reference's); otherwise the
+        noise of pair (n, t) is drawn in the kernels from `seed` (default: a fresh one from torch's generator) as
+        `philox_normal(N, frames, seed, t)[n]`, whatever the packing.
+
+        The one deviation: model_kwargs goes to q_sample, which the reference's loop omits (:1574) -- its
+        InpaintingGaussianDiffusion.q_sample then fails on None['y'].  Under that class the noise is masked as its q_sample masks it."""
+        with th.no_grad():
+            dev = x_start.device
+            self._variance_tables()                        # learned variances stay refused
+            sch = self._schedule(dev)                      # (refuses a CPU tensor)
+            n, T = int(x_start.shape[0]), self.num_timesteps
+            if noise is not None:
+                assert tuple(noise.shape) == (T,) + tuple(x_start.shape), \
+                    f"noise: shape {tuple(noise.shape)} is not {(T,) + tuple(x_start.shape)} (one draw per timestep index)"
+                noise = noise.to(dev)
+                seed = 0
+            elif seed is None:
+                seed = int(th.randint(0, 2 ** 31 - 1, (1,)).item())
+            nmask = self._noise_mask(model_kwargs)
+            pair = self._inpaint_pair(model_kwargs)
+            plan = vb_row_plan(n, T, rows)
+            if progress:
+                from tqdm.auto import tqdm
+                plan = tqdm(plan)
+            terms = []
+            for clip, t in plan:
+                cd, td = th.tensor(clip, device=dev), th.tensor(t, device=dev)
+                z = None if noise is None else noise[td, cd]
+                x_t = sch.vb_diffuse(x_start, cd, td, noise=z, seed=seed, mask=nmask)
+                kw = vb_gather_kwargs(model_kwargs, clip, cd, n)
+                terms.append(self._vb_rows(model, x_start, x_t, cd, td, z, seed, clip_denoised, kw, pair, False)[0])
+            terms = th.cat(terms).view(T, n, 4).permute(1, 0, 2)         # rows are (t descending, clip): -> [N, T, 4], column 0 = t = T - 1
+            prior_bpd = self._prior_bpd(x_start)
+            vb = terms[..., 0].contiguous()
+            return {"total_bpd": vb.sum(dim=1) + prior_bpd, "prior_bpd": prior_bpd, "vb": vb,
+                    "xstart_mse": terms[..., 1].contiguous(), "mse": terms[..., 2].contiguous()}
 
     # ------------------------------------------------------------------------------ fine-tune loss
     def few_shot_style_finetune_losses(self, model, x_start, t, x_content_start, x_style_start, skip_steps=700,

@@ -243,6 +243,83 @@ class Schedule:
                                        x.numel() // B, int(mean_type), int(bool(clip_denoised)), N.ptr(sample), N.stream_ptr(dev)))
         return sample
 
+    # the variational-bound evaluation on (clip, timestep) rows (csrc/mst_vb.h) -------------------
+    def _vb_rows(self, x_start, clip, t):
+        """(x_start, clip, t, N, per_clip) of a row launch: the indices are checked HERE, on the caller's tensors, before they go to the
+        device -- the kernels gather by them and make no check of their own."""
+        n = int(x_start.shape[0])
+        clip, t = (torch.as_tensor(v).reshape(-1).to(torch.int64) for v in (clip, t))
+        if clip.numel() < 1 or clip.numel() != t.numel():
+            raise ValueError(f"vb rows: {clip.numel()} clip indices for {t.numel()} timesteps (one pair per row, at least one row)")
+        for v, hi, what in ((clip, n, "clip index"), (t, self.num_steps, "timestep index")):
+            if v.device.type == "cpu" and (int(v.min()) < 0 or int(v.max()) >= hi):
+                raise IndexError(f"vb rows: {what} out of [0, {hi})")
+        dev = x_start.device
+        x_start = _f32c(x_start, dev, "x_start")
+        return x_start, clip.to(dev).contiguous(), t.to(dev).contiguous(), n, x_start.numel() // n
+
+    @staticmethod
+    def _vb_layout(x_start, noise):
+        """(feats, frames) a drawn noise needs -- x_start as [N, F, 1, T] -- or (0, 0) with a noise buffer."""
+        if noise is not None:
+            return 0, 0
+        if x_start.dim() != 4 or x_start.shape[2] != 1:
+            raise ValueError(f"a drawn noise needs x_start as [N, feats, 1, frames] (got {tuple(x_start.shape)}); pass noise= otherwise")
+        return int(x_start.shape[1]), int(x_start.shape[3])
+
+    def vb_diffuse(self, x_start, clip, t, noise=None, seed=0, mask=None):
+        """x_t [R, ...] of the rows (clip[r], t[r]): `q_sample(x_start[clip], t, noise, mask[clip])` bit for bit without the gathers.
+        x_start / mask are per clip ([N, ...]); noise is per row ([R, ...]) or None -- the row's noise is then drawn in the kernel as
+        `philox_normal(N, frames, seed, t[r])[clip[r]]`, whatever the packing.  clip / t given as CPU tensors or lists are range-checked
+        (a device tensor would cost a synchronisation: its producer owes the check)."""
+        x_start, clip, t, n, per = self._vb_rows(x_start, clip, t)
+        dev, R = x_start.device, clip.numel()
+        shape = (R,) + tuple(x_start.shape[1:])
+        F, T = self._vb_layout(x_start, noise)
+        noise = None if noise is None else _operand(noise, shape, "noise", RULE_EQUAL, dev)
+        mask, _ = _mask_pair(mask, None, x_start.shape, dev)
+        out = torch.empty(shape, device=dev, dtype=torch.float32)
+        N.check(N.lib().mst_vb_diffuse(self.handle, N.ptr(x_start), N.ptr(noise), N.ptr(mask), N.ptr(clip), N.ptr(t), R, per, F, T,
+                                       int(seed), N.ptr(out), N.stream_ptr(dev)))
+        return out
+
+    def vb_terms(self, true_log_variance, x_start, x_t, model_output, clip, t, noise=None, seed=0, mask=None, motion=None,
+                 clip_denoised=True, mean_type=0, want_xstart=False):
+        """(terms [R, 4], x0-hat [R, ...] or None) of the rows (clip[r], t[r]) given the model's raw output on x_t: terms[r] = (the
+        bound's term in bits, mean (x0hat - x_start)^2, mean (eps - noise)^2, rms of x0hat), `_vb_terms_bpd` plus the two MSEs of
+        `calc_bpd_loop`.  true_log_variance: posterior_log_variance_clipped as a float32 device tensor [num_steps].  mask / motion: the
+        inpainting pair per clip ([N, ...]), both or neither.  noise: what x_t was diffused with, per row, or None and the `seed` of
+        `vb_diffuse`."""
+        x_start, clip, t, n, per = self._vb_rows(x_start, clip, t)
+        dev, R = x_start.device, clip.numel()
+        shape = (R,) + tuple(x_start.shape[1:])
+        F, T = self._vb_layout(x_start, noise)
+        x_t = _operand(x_t, shape, "x_t", RULE_EQUAL, dev)
+        mo = _operand(model_output, shape, "model_output", RULE_EQUAL, dev)
+        noise = None if noise is None else _operand(noise, shape, "noise", RULE_EQUAL, dev)
+        if (mask is None) != (motion is None):
+            raise ValueError("vb_terms: the inpainting pair is mask AND motion, or neither")
+        mask, motion = _mask_pair(mask, motion, x_start.shape, dev)
+        tlv = _f32c(true_log_variance, dev, "true_log_variance")
+        assert tlv.shape == (self.num_steps,), f"true_log_variance: shape {tuple(tlv.shape)} is not ({self.num_steps},)"
+        out = torch.empty((R, 4), device=dev, dtype=torch.float32)
+        xs = torch.empty(shape, device=dev, dtype=torch.float32) if want_xstart else None
+        N.check(N.lib().mst_vb_terms(self.handle, N.ptr(tlv), N.ptr(x_start), N.ptr(x_t), N.ptr(mo), N.ptr(noise), N.ptr(mask),
+                                     N.ptr(motion), N.ptr(clip), N.ptr(t), R, per, F, T, int(seed), int(mean_type),
+                                     int(bool(clip_denoised)), N.ptr(out), N.ptr(xs), N.stream_ptr(dev)))
+        return out, xs
+
+    def vb_prior(self, x_start, sqrt_ac_last, log_1m_ac_last):
+        """`_prior_bpd` [N]: mean_flat(normal_kl(sqrt_ac_last x_start, log_1m_ac_last, 0, 0)) / ln 2; the two scalars are the last
+        entries of sqrt_alphas_cumprod and log_one_minus_alphas_cumprod (no row of enum mst_table), read as float32."""
+        dev = x_start.device
+        x_start = _f32c(x_start, dev, "x_start")
+        n = x_start.shape[0]
+        out = torch.empty((n,), device=dev, dtype=torch.float32)
+        N.check(N.lib().mst_vb_prior(self.handle, N.ptr(x_start), n, x_start.numel() // n, float(np.float32(sqrt_ac_last)),
+                                     float(np.float32(log_1m_ac_last)), N.ptr(out), N.stream_ptr(dev)))
+        return out
+
 
 def guide_args(x, grad=None, target=None, mask=None, weight=None, follow_schedule=False):
     """(MstGuideArgs, tensors it points to) for a step or loop on `x` ([B,F,1,T]): grad -> MST_GUIDE_GRADIENT (the gradient of one

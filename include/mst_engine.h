@@ -398,6 +398,43 @@ int mst_philox_normal(float* out_dev, int32_t batch, int32_t feats, int32_t fram
                       uint32_t step, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * The variational-bound evaluation on timestep-batched rows (csrc/mst_vb.h): calc_bpd_loop (gaussian_diffusion.py:1547-1602) visits
+ * its timesteps independently of each other, so (clip, timestep) pairs are packed into full model batches.  A ROW r is the pair
+ * (clip_dev[r], t_dev[r]), both int64 [rows], in any order.  x_start / mask / motion are per CLIP ([N][per_clip], gathered by
+ * clip_dev[r]); x_t, the model output, a noise buffer, x0-hat are per ROW ([rows][per_clip]).
+ *   mst_vb_diffuse   q_sample on gathered operands (gaussian_diffusion.py:267-285, :1573-1574; inpainting_gaussian_diffusion.py:6-23):
+ *                    out[r] = sqrt_ac[t] x_start[clip] + sqrt_1m_ac[t] z (1 - mask[clip]), the expression of mst_q_sample bit for bit.
+ *                    mask_dev may be NULL.  noise_dev: z as [rows][per_clip], or NULL -- z is then drawn: row r gets
+ *                    mst_philox_normal(N, feats, frames, seed, step = t[r])[clip[r]], so the noise of a (clip, timestep) pair does not
+ *                    depend on the packing; feats * frames must be per_clip.
+ *   mst_vb_terms     _vb_terms_bpd (:1281-1314 with p_mean_variance :341-412, losses.py:12-77) and the two MSEs of the loop
+ *                    (:1586-1588): out_dev [rows][4] = (vb term in bits, mean (x0hat - x_start)^2, mean (eps - z)^2, rms of x0-hat) over
+ *                    ALL per_clip elements (mean_flat: no frame mask, as the reference).  The inpainting blend acts on the raw output,
+ *                    then mean_type (as mst_step_epilogue_mt), then clip_denoised.  t != 0: normal_kl(true posterior, model posterior);
+ *                    true_logvar_dev is posterior_log_variance_clipped as float32 [num_steps] (the schedule's log-variance row is the
+ *                    MODEL's: they differ under FIXED_LARGE); for mean types 0 and 1 the means' difference is coef1 (x_start - x0hat).
+ *                    t == 0: minus discretized_gaussian_log_likelihood, evaluated in double.  z: noise_dev, or NULL and the draw of
+ *                    mst_vb_diffuse.  xstart_out_dev ([rows][per_clip]) may be NULL.  Sums are accumulated in double in a fixed order,
+ *                    one workgroup per row, no atomics: a row's four numbers do not depend on the other rows of the call.
+ *   mst_vb_prior     _prior_bpd (:1529-1545): out_dev[n] = mean_flat(normal_kl(sqrt_ac_last x_start[n], log_1m_ac_last, 0, 0)) / ln 2,
+ *                    the two scalars being sqrt_alphas_cumprod[-1] and log_one_minus_alphas_cumprod[-1] as float32 (the second is
+ *                    no row of enum mst_table); the schedule names the device the launch goes to.
+ * THE CALLER IS TRUSTED as in the stand-alone elementwise section: every operand is read as base + i over its full size, no check that
+ * would cost a synchronisation is made, and clip_dev[r] in [0, N), t_dev[r] in [0, num_steps) are the caller's to check (the Python
+ * handles do).  Refused here by name: null operands, rows / batch / per_clip < 1, an unknown mean_type, a draw without feats / frames
+ * or with feats * frames != per_clip, a mask without a motion in mst_vb_terms.
+ * ----------------------------------------------------------------------------------------- */
+int mst_vb_diffuse(const mst_schedule* s, const float* x_start_dev, const float* noise_dev, const float* mask_dev,
+                   const int64_t* clip_dev, const int64_t* t_dev, int32_t rows, int64_t per_clip, int32_t feats, int32_t frames,
+                   uint64_t seed, float* out_dev, void* stream);
+int mst_vb_terms(const mst_schedule* s, const float* true_logvar_dev, const float* x_start_dev, const float* x_t_dev,
+                 const float* model_out_dev, const float* noise_dev, const float* mask_dev, const float* motion_dev,
+                 const int64_t* clip_dev, const int64_t* t_dev, int32_t rows, int64_t per_clip, int32_t feats, int32_t frames,
+                 uint64_t seed, int32_t mean_type, int32_t clip_denoised, float* out_dev, float* xstart_out_dev, void* stream);
+int mst_vb_prior(const mst_schedule* s, const float* x_start_dev, int32_t batch, int64_t per_clip, float sqrt_ac_last, float log_1m_ac_last, float* out_dev,
+                 void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * Training path of the TRAINABLE encoder stack: StyleDiffusion.seqTransEncoder, 8 x
  * nn.TransformerEncoderLayer(d_model=512, nhead=4, dim_feedforward=1024, dropout=0.1, gelu),
  * model/mdm_forstyledataset.py:539-546, called at :622 inside the graph that
