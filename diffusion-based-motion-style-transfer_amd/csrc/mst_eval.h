@@ -8,11 +8,14 @@
 //   k_gru_step     one time step of both directions of torch's GRU (gates r, z, n): W_hh[slice] h for 16 units x 3 gates x 16 clips a
 //                  workgroup, the gate arithmetic fused, h double-buffered in global memory by the host loop.
 //   k_ln_leaky     LayerNorm (two-pass, biased variance) + LeakyReLU, one wave a row.
-//   k_dist_rank    sqrt(max(-2 a.b + |a|^2 + |b|^2, 0)) and per row the number of entries strictly below the diagonal one.
+//   k_dist_rank    sqrt(-2 a.b + |a|^2 + |b|^2) and per row the number of entries strictly below the diagonal one.  Only a radicand
+//                  below zero (rounding) is clamped to 0: NaN and +inf pass through the root, so a non-finite embedding row gives a
+//                  non-finite row of distances, never 0.  A row whose diagonal distance is not finite gets rank n2: it is in no top-k.
 //   k_col_mean_f64 / k_cov_f64   np.cov(rowvar=False) of fp32 rows in double.
 //   k_pair_norms   |A[i_k] - B[j_k]|, summed in fp32.
 // No atomics; every result is a fixed-order sum, so a row's value does not depend on what else is in the batch.
 #pragma once
+#include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -233,21 +236,23 @@ __global__ __launch_bounds__(256) void k_dist_rank(const float* __restrict__ e1,
         bsq = eval_wave_sum(bsq);
         if (lane == 0) {
             const float rad = (-2.f * dot + asq) + bsq;      // the reference's order: d1 + d2, then + d3
-            dist[(int64_t)i * n2 + j] = sqrtf(rad > 0.f ? rad : 0.f);
+            dist[(int64_t)i * n2 + j] = sqrtf(rad < 0.f ? 0.f : rad);       // NaN is not below zero: it goes through the root, as +inf does
         }
     }
     if (!rank) return;
     __syncthreads();                                         // the row of distances is written (workgroup scope)
     int c = 0;
+    bool ranked = false;
     if (i < n2) {
         const float diag = dist[(int64_t)i * n2 + i];
+        ranked = fabsf(diag) <= FLT_MAX;                     // false for NaN and inf
         for (int j = tid; j < n2; j += 256) c += dist[(int64_t)i * n2 + j] < diag ? 1 : 0;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
     if (lane == 0) cnt[wave] = c;
     __syncthreads();
-    if (tid == 0) rank[i] = i < n2 ? cnt[0] + cnt[1] + cnt[2] + cnt[3] : -1;
+    if (tid == 0) rank[i] = i < n2 ? (ranked ? cnt[0] + cnt[1] + cnt[2] + cnt[3] : n2) : -1;
 }
 
 __global__ void k_col_mean_f64(const float* __restrict__ a, int n, int d, double* __restrict__ mean) {

@@ -6,9 +6,13 @@ device).  Scalars come back as Python / numpy numbers either way.  The random in
 and are the reference's own `np.random.choice` calls in its order, so a seeded run picks the same pairs.
 
 Stated differences from the reference:
-  * a distance whose radicand -2 a.b + |a|^2 + |b|^2 rounds below zero is 0 here, NaN there;
+  * a distance whose radicand -2 a.b + |a|^2 + |b|^2 rounds below zero is 0 here, NaN there.  Only a negative radicand is clamped: a
+    NaN or infinite embedding row gives non-finite distances here as there, never 0;
   * `calculate_R_precision` counts, per row, the entries strictly below the diagonal one (top-k is rank < k) where the reference
     argsorts: the two differ only where a row holds an exact tie with its diagonal entry, which argsort resolves by position;
+  * a row whose diagonal distance is not finite gets rank N here and so is a hit at no k.  The reference's argsort puts NaN last, so
+    an all-NaN row is ranked there by position (row 0 of a batch would hit at top-1); a NaN entry elsewhere in a row is "not below"
+    the diagonal in both;
   * `calculate_activation_statistics` returns the mean in float64 (summed in double on the device); the reference's `np.mean` of
     float32 rows is float32.  The covariance is float64 in both.
 The 512 x 512 matrix square root of the Frechet distance runs in float64 on the host (scipy.linalg.sqrtm)."""
@@ -48,7 +52,8 @@ def _dist_rank(e1, e2, what, want_rank):
 
 
 def euclidean_distance_matrix(matrix1, matrix2):
-    """[N1, D], [N2, D] -> [N1, N2] float32: sqrt(-2 a.b + |a|^2 + |b|^2), the reference's expansion, clamped at 0."""
+    """[N1, D], [N2, D] -> [N1, N2] float32: sqrt(-2 a.b + |a|^2 + |b|^2), the reference's expansion; a radicand below zero is 0, a
+    non-finite row stays non-finite."""
     dist, _, was = _dist_rank(matrix1, matrix2, "euclidean_distance_matrix", False)
     return _back(dist, was)
 

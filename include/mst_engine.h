@@ -809,9 +809,12 @@ int mst_rot_decode_max_frames(int32_t joints);
  *
  * mst_eval_layernorm: y = LeakyReLU?((x - mean) / sqrt(var + eps) * gamma + beta) per row, two-pass, biased variance.
  *
- * mst_eval_dist_rank: dist[i][j] = sqrt(max(-2 e1[i].e2[j] + |e1[i]|^2 + |e2[j]|^2, 0)) in fp32 (the reference's expansion; it yields
- * NaN where rounding makes the radicand negative, this 0).  rank (optional, n1 == n2): per row the number of entries strictly below the
- * diagonal one -- calculate_R_precision's top-k is rank < k.  d <= 8192.
+ * mst_eval_dist_rank: dist[i][j] = sqrt(-2 e1[i].e2[j] + |e1[i]|^2 + |e2[j]|^2) in fp32 (the reference's expansion; it yields NaN
+ * where rounding makes the radicand negative, this 0).  Only a radicand below zero is clamped: NaN and +inf pass through the root as
+ * they do there, so a non-finite row of e1 (e2) gives a non-finite row (column) of dist, never 0.  rank (optional,
+ * n1 == n2): per row the number of entries strictly below the diagonal one -- calculate_R_precision's top-k is rank < k; a NaN entry is
+ * not below anything, and a row whose diagonal entry is not finite gets rank n2, in no top-k (the reference's argsort puts NaN last and
+ * ranks an all-NaN row by position).  d <= 8192.
  *
  * mst_eval_cov: mean[d] and, when cov is given (n >= 2), the (n - 1)-normalised covariance [d][d] of fp32 rows a[n][d], in double, the
  * mean subtracted before the products (np.cov(rowvar=False)).

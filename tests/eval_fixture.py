@@ -224,13 +224,19 @@ def sigmoid(x):
 
 def gru_last(sd, x, steps, dtype):
     """torch's bidirectional GRU over packed sequences: x [B, L, H], steps [B] -> [B, 2 H] (forward's final state, then backward's)."""
-    B, L, H = x.shape
+    proj = [x @ np.asarray(sd[f"gru.weight_ih_l0{r}"], dtype).T + np.asarray(sd[f"gru.bias_ih_l0{r}"], dtype) for r in ("", "_reverse")]
+    return gru_last_projected(sd, proj, steps, dtype)
+
+
+def gru_last_projected(sd, proj, steps, dtype):
+    """The recurrence of `gru_last` on given input projections: proj[direction] [B, L, 3 H] = W_ih x + b_ih (gates r, z, n).  A position
+    that no step of its clip reaches is never read."""
+    B, L, H = proj[0].shape[0], proj[0].shape[1], proj[0].shape[2] // 3
     steps = np.asarray(steps, np.int64)
     out = []
     for d, r in enumerate(("", "_reverse")):
-        wih, whh = np.asarray(sd[f"gru.weight_ih_l0{r}"], dtype), np.asarray(sd[f"gru.weight_hh_l0{r}"], dtype)
-        bih, bhh = np.asarray(sd[f"gru.bias_ih_l0{r}"], dtype), np.asarray(sd[f"gru.bias_hh_l0{r}"], dtype)
-        gi_all = x @ wih.T + bih
+        whh, bhh = np.asarray(sd[f"gru.weight_hh_l0{r}"], dtype), np.asarray(sd[f"gru.bias_hh_l0{r}"], dtype)
+        gi_all = np.asarray(proj[d], dtype)
         h = np.repeat(np.asarray(sd["hidden"], dtype)[d], B, 0)
         for s in range(int(steps.max())):
             act = np.nonzero(steps > s)[0]
@@ -282,8 +288,13 @@ def euclidean_distance_matrix(m1, m2, dtype):
 
 
 def diagonal_ranks(m1, m2, dtype):
-    d = euclidean_distance_matrix(m1, m2, dtype)
-    return (d < np.diag(d)[:, None]).sum(1)
+    """Entries strictly below the diagonal one, per row; a NaN entry is not below anything (numpy's `<`), and a row whose diagonal
+    distance is not finite ranks last: N2, in no top-k."""
+    with np.errstate(invalid="ignore"):
+        d = euclidean_distance_matrix(m1, m2, dtype)
+        diag = np.diag(d)
+        below = (d < diag[:, None]).sum(1)
+    return np.where(np.isfinite(diag), below, d.shape[1])
 
 
 def r_precision(m1, m2, top_k, dtype):
