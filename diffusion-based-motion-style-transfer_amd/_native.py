@@ -39,6 +39,16 @@ class MstGuideArgs(C.Structure):
                 ("mask_dev", C.c_void_p), ("weight_dev", C.c_void_p)]
 
 
+class MstClipLayer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "ln1_g", "ln1_b", "wqkv", "bqkv", "wo", "bo", "ln2_g", "ln2_b", "w1", "b1", "w2", "b2")]
+
+
+class MstClipWeights(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("layers", "vocab", "context", "width", "heads", "ffn")] + \
+               [(n, C.c_void_p) for n in ("tok_emb", "pos_emb", "lnf_g", "lnf_b", "proj")] + [("layer", C.POINTER(MstClipLayer))]
+
+
 # name -> (restype, argtypes); must list every function include/mst_engine.h declares
 SIGNATURES = {
     "mst_last_error": (C.c_char_p, []),
@@ -165,6 +175,11 @@ SIGNATURES = {
     "mst_eval_cov": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mst_eval_pair_norms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_void_p]),
+    "mst_clip_pack_weight": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mst_clip_plan": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int64)]),
+    "mst_clip_encode": (C.c_int, [C.POINTER(MstClipWeights), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mst_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "mst_profile_event_overhead_us": (C.c_float, [C.c_void_p]),
     "mst_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(C.c_int32),

@@ -39,6 +39,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_window.h"
 #include "mst_plan.h"
 #include "mst_vb.h"
+#include "mst_clip.h"
 
 using namespace mst;
 
@@ -3926,6 +3927,110 @@ extern "C" int mst_eval_pair_norms(const float* a, const float* b, const int32_t
     if (!a || !b || !ia || !ib || !out) return fail("mst_eval_pair_norms: null operand");
     if (pairs < 1 || na < 1 || nb < 1 || d < 1) return fail("mst_eval_pair_norms: pairs %d, rows %d / %d, features %d: each at least 1", pairs, na, nb, d);
     hipLaunchKernelGGL(k_pair_norms, dim3((pairs + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, b, ia, ib, pairs, na, nb, d, out);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ CLIP text tower (mst_clip.h)
+// workspace of M packed rows: x f32 [M][512] | h f16 [M][512] | qkv f16 [M][1536] | att f16 [M][512] | u f16 [M][2048]
+static int64_t clip_workspace_bytes(int64_t rows) { return rows * (CLIP_D * 4 + CLIP_D * 2 + 3 * CLIP_D * 2 + CLIP_D * 2 + CLIP_FF * 2); }
+
+extern "C" int mst_clip_pack_weight(const void* src, int32_t src_is_f16, int32_t n, int32_t k, void* dst, void* stream) {
+    if (!src || !dst) return fail("mst_clip_pack_weight: null operand");
+    if (n < 16 || n % 16) return fail("mst_clip_pack_weight: %d output rows are no multiple of 16", n);
+    if (k < 32 || k % 32) return fail("mst_clip_pack_weight: %d input columns are no multiple of 32", k);
+    if (!eval_aligned16(src) || !eval_aligned16(dst)) return fail("mst_clip_pack_weight: src and dst are accessed 16 bytes at a time: unaligned pointer");
+    const int64_t items = (int64_t)n * k / 8;
+    const dim3 grid((unsigned)((items + 255) / 256));
+    if (src_is_f16)
+        hipLaunchKernelGGL(k_clip_pack<f16>, grid, dim3(256), 0, (hipStream_t)stream, (const f16*)src, (f16*)dst, n, k);
+    else
+        hipLaunchKernelGGL(k_clip_pack<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)src, (f16*)dst, n, k);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_clip_plan(const int32_t* lens_host, int32_t batch, int32_t context, int32_t* offsets_host, int32_t* total_rows,
+                             int64_t* workspace_bytes) {
+    if (!lens_host || !offsets_host || !total_rows || !workspace_bytes) return fail("mst_clip_plan: null argument");
+    if (batch < 1 || batch > 65535) return fail("mst_clip_plan: batch %d outside 1..65535", batch);
+    if (context < 1 || context > CLIP_CTX) return fail("mst_clip_plan: context %d outside 1..%d", context, CLIP_CTX);
+    int64_t rows = 0;
+    for (int b = 0; b < batch; b++) {
+        if (lens_host[b] < 1 || lens_host[b] > context)
+            return fail("mst_clip_plan: prompt %d has %d live rows, outside 1..%d (context)", b, lens_host[b], context);
+        offsets_host[b] = (int32_t)rows;
+        rows += lens_host[b];
+    }
+    *total_rows = (int32_t)rows;
+    *workspace_bytes = clip_workspace_bytes(rows);
+    return 0;
+}
+
+extern "C" int mst_clip_encode(const mst_clip_weights* w, const int32_t* ids, int32_t batch, int32_t ids_stride, const int32_t* lens,
+                               const int32_t* offsets, int32_t total_rows, void* workspace, int64_t workspace_bytes, float* out, void* stream) {
+    if (!w || !ids || !lens || !offsets || !workspace || !out) return fail("mst_clip_encode: null operand");
+    if (w->width != CLIP_D) return fail("mst_clip_encode: width %d: only the %d-wide tower is built", w->width, CLIP_D);
+    if (w->heads != CLIP_H) return fail("mst_clip_encode: heads %d: only %d heads of %d are built", w->heads, CLIP_H, CLIP_HD);
+    if (w->ffn != CLIP_FF) return fail("mst_clip_encode: ffn %d: only the %d-wide FFN is built", w->ffn, CLIP_FF);
+    if (w->layers < 1) return fail("mst_clip_encode: layers %d: at least 1", w->layers);
+    if (w->vocab < 1) return fail("mst_clip_encode: vocab %d: at least 1", w->vocab);
+    if (w->context < 1 || w->context > CLIP_CTX) return fail("mst_clip_encode: context %d outside 1..%d", w->context, CLIP_CTX);
+    if (!w->tok_emb_dev || !w->pos_emb_dev || !w->lnf_g_dev || !w->lnf_b_dev || !w->proj_dev || !w->layer_host)
+        return fail("mst_clip_encode: null tensor in the weight table");
+    for (int l = 0; l < w->layers; l++) {
+        const mst_clip_layer& y = w->layer_host[l];
+        if (!y.ln1_g_dev || !y.ln1_b_dev || !y.wqkv_dev || !y.bqkv_dev || !y.wo_dev || !y.bo_dev || !y.ln2_g_dev || !y.ln2_b_dev || !y.w1_dev ||
+            !y.b1_dev || !y.w2_dev || !y.b2_dev)
+            return fail("mst_clip_encode: null tensor in layer %d of the weight table", l);
+    }
+    if (batch < 1 || batch > 65535) return fail("mst_clip_encode: batch %d outside 1..65535", batch);
+    if (ids_stride < 1 || ids_stride > w->context) return fail("mst_clip_encode: %d ids a prompt outside 1..%d (context)", ids_stride, w->context);
+    if (total_rows < batch || (int64_t)total_rows > (int64_t)batch * ids_stride)
+        return fail("mst_clip_encode: %d packed rows outside %d..%lld (batch .. batch * ids a prompt)", total_rows, batch, (long long)batch * ids_stride);
+    if (workspace_bytes < clip_workspace_bytes(total_rows))
+        return fail("mst_clip_encode: workspace of %lld bytes < %lld (mst_clip_plan)", (long long)workspace_bytes, (long long)clip_workspace_bytes(total_rows));
+    if (!eval_aligned16(workspace) || !eval_aligned16(w->tok_emb_dev) || !eval_aligned16(w->pos_emb_dev))
+        return fail("mst_clip_encode: workspace and embeddings are accessed 16 bytes at a time: unaligned pointer");
+    const hipStream_t st = (hipStream_t)stream;
+    const int M = total_rows;
+    char* ws = (char*)workspace;
+    float* x = (float*)ws;
+    f16* h = (f16*)(ws + (size_t)M * CLIP_D * 4);
+    f16* qkv = h + (size_t)M * CLIP_D;
+    f16* att = qkv + (size_t)M * 3 * CLIP_D;
+    f16* u = att + (size_t)M * CLIP_D;
+    const unsigned mt = (unsigned)((M + CLIP_BM - 1) / CLIP_BM);
+
+    ClipEmbedArgs ea{ids, lens, offsets, (const f16*)w->tok_emb_dev, (const f16*)w->pos_emb_dev, w->layer_host[0].ln1_g_dev,
+                     w->layer_host[0].ln1_b_dev, x, h, ids_stride, w->vocab, w->context, M};
+    hipLaunchKernelGGL(k_clip_embed, dim3(batch), dim3(256), 0, st, ea);
+    HIPCHECK(hipGetLastError());
+    for (int l = 0; l < w->layers; l++) {
+        const mst_clip_layer& y = w->layer_host[l];
+        const bool last = l == w->layers - 1;
+        ClipGemmArgs g{};
+        g.M = M;
+        g.a = h; g.w = (const f16*)y.wqkv_dev; g.bias = y.bqkv_dev; g.out = qkv; g.N = 3 * CLIP_D; g.K = CLIP_D;
+        hipLaunchKernelGGL(k_clip_gemm<kClipStore>, dim3(mt, 3 * CLIP_D / CLIP_BN), dim3(512), 0, st, g);
+        HIPCHECK(hipGetLastError());
+        ClipAttnArgs aa{qkv, lens, offsets, att, M};
+        hipLaunchKernelGGL(k_clip_attn, dim3(CLIP_H, batch), dim3(256), 0, st, aa);
+        HIPCHECK(hipGetLastError());
+        g.a = att; g.w = (const f16*)y.wo_dev; g.bias = y.bo_dev; g.x = x; g.g = y.ln2_g_dev; g.b = y.ln2_b_dev; g.out = h; g.N = CLIP_D; g.K = CLIP_D;
+        hipLaunchKernelGGL(k_clip_gemm<kClipResid>, dim3(mt, 1), dim3(512), 0, st, g);
+        HIPCHECK(hipGetLastError());
+        g.a = h; g.w = (const f16*)y.w1_dev; g.bias = y.b1_dev; g.x = nullptr; g.g = nullptr; g.b = nullptr; g.out = u; g.N = CLIP_FF; g.K = CLIP_D;
+        hipLaunchKernelGGL(k_clip_gemm<kClipGelu>, dim3(mt, CLIP_FF / CLIP_BN), dim3(512), 0, st, g);
+        HIPCHECK(hipGetLastError());
+        g.a = u; g.w = (const f16*)y.w2_dev; g.bias = y.b2_dev; g.x = x; g.out = h; g.N = CLIP_D; g.K = CLIP_FF;
+        g.g = last ? nullptr : w->layer_host[l + 1].ln1_g_dev;
+        g.b = last ? nullptr : w->layer_host[l + 1].ln1_b_dev;
+        hipLaunchKernelGGL(k_clip_gemm<kClipResid>, dim3(mt, 1), dim3(512), 0, st, g);
+        HIPCHECK(hipGetLastError());
+    }
+    ClipFinalArgs fa{x, lens, offsets, w->lnf_g_dev, w->lnf_b_dev, (const f16*)w->proj_dev, out, M};
+    hipLaunchKernelGGL(k_clip_final, dim3(batch), dim3(512), 0, st, fa);
     HIPCHECK(hipGetLastError());
     return 0;
 }

@@ -11,8 +11,9 @@ The arithmetic has ONE implementation, the HIP library; the nn.Module containers
     kernels (model/native_stack.py: activation tape + dropout forward, HIP backward).
 There is no torch-op evaluation of the stacks here: CPU tensors raise.  (The tests carry their own fp32 reference,
 tests/torch_reference.py, and install it on an instance when they need one.)
-CLIP stays third-party: `encode_text` uses the `clip` package when it is installed, a callable set
-with `set_text_encoder`, or a precomputed `y['text_embed']` ([B, clip_dim]).
+CLIP: `encode_text` uses a callable set with `set_text_encoder` (`use_native_text_encoder` sets the
+package's own GPU text tower and tokenizer, model/clip_text.py), else the `clip` package when it is
+installed; a precomputed `y['text_embed']` ([B, clip_dim]) bypasses it.
 """
 import contextlib
 import os
@@ -344,6 +345,22 @@ class MDM(nn.Module, _EngineHost):
     def set_text_encoder(self, fn):
         """fn(list[str]) -> float tensor [B, clip_dim]; replaces CLIP when it is not installed."""
         self._text_encoder = fn
+
+    def use_native_text_encoder(self, weights, bpe_path):
+        """encode_text on the GPU with this package alone (model/clip_text.py): `weights` a CLIP checkpoint file (ViT-B-32.pt, a
+        torch.save dict, .safetensors), a state dict in OpenAI or Hugging Face key layout, or a ClipTextEncoder; `bpe_path` the
+        merges file of CLIP's tokenizer.  Returns the encoder it set."""
+        from .clip_text import ClipTextEncoder, SimpleTokenizer
+        device = next(self.parameters()).device
+        if isinstance(weights, ClipTextEncoder):
+            enc = weights
+        elif isinstance(weights, dict):
+            enc = ClipTextEncoder.from_state_dict(weights, device)
+        else:
+            enc = ClipTextEncoder.from_file(weights, device)
+        enc.tokenizer, enc.dataset = SimpleTokenizer(bpe_path), self.dataset
+        self.set_text_encoder(enc)
+        return enc
 
     def mask_cond(self, cond, force_mask=False):
         return _mask_cond(self, cond, force_mask)

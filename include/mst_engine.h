@@ -834,6 +834,59 @@ int mst_eval_cov(const float* a_dev, int32_t n, int32_t d, double* mean_dev, dou
 int mst_eval_pair_norms(const float* a_dev, const float* b_dev, const int32_t* ia_dev, const int32_t* ib_dev, int32_t pairs, int32_t na,
                         int32_t nb, int32_t d, float* out_dev, void* stream);
 
+/* -----------------------------------------------------------------------------------------
+ * CLIP's text tower (csrc/mst_clip.h).  Replaces: clip_model.encode_text of model/mdm_forstyledataset.py's encode_text -- token and
+ * positional embedding, `layers` pre-LayerNorm blocks (width 512, 8 heads of 64, causal attention, FFN 2048 with QuickGELU), ln_final on
+ * the row of the end-of-text token and `@ text_projection`.  Only the live rows of a prompt (0 .. its end-of-text position) are
+ * computed, packed into one row range for the whole batch.  The residual stream is fp32 throughout; GEMM operands are f16
+ * (v_mfma_f32_16x16x32_f16, fp32 accumulation); LayerNorm, softmax and QuickGELU are fp32.  No atomics, no split-K: every output is a
+ * fixed-order sum that depends neither on the batch nor on where the prompt's rows lie, so a prompt encodes to the same bits alone
+ * and in any batch.  All pointers but `layer_host` and the plan's arrays are device pointers; every launch goes to `stream`; nothing
+ * is allocated and nothing synchronises.
+ *
+ * mst_clip_pack_weight: a row-major [n][k] matrix (out features x in features; float32, or f16 when src_is_f16) -> n * k halves in the
+ * MFMA fragment order the GEMMs read.  n a multiple of 16, k of 32.  For in_proj_weight [1536][512], out_proj [512][512], c_fc
+ * [2048][512] and c_proj [512][2048].
+ * mst_clip_plan (host only): lens_host[b] = live rows of prompt b (end-of-text position + 1, 1 .. context) -> offsets_host[b], the
+ * first packed row of prompt b, their total and the workspace a call needs.
+ * mst_clip_encode: ids [batch][ids_stride] int32 (ids_stride <= context; an id outside 0 .. vocab - 1 is clamped, the caller
+ * validates), lens / offsets as planned (device copies; rows a mismatched plan would put outside 0 .. total_rows - 1 are not
+ * computed) -> out float32 [batch][512].  The table: tok_emb f16 [vocab][512], pos_emb f16 [context][512], proj f16 [512 in][512 out]
+ * (text_projection as stored, applied as x @ P), LayerNorm vectors and biases float32, the four matrices of a layer packed.
+ * Width 512, 8 heads and FFN 2048 are the only tower built: anything else is refused by name.
+ * ----------------------------------------------------------------------------------------- */
+typedef struct mst_clip_layer {
+    const float* ln1_g_dev;
+    const float* ln1_b_dev;
+    const void* wqkv_dev;  /* packed [1536][512], rows q | k | v */
+    const float* bqkv_dev;
+    const void* wo_dev;    /* packed [512][512] */
+    const float* bo_dev;
+    const float* ln2_g_dev;
+    const float* ln2_b_dev;
+    const void* w1_dev;    /* packed [2048][512] */
+    const float* b1_dev;
+    const void* w2_dev;    /* packed [512][2048] */
+    const float* b2_dev;
+} mst_clip_layer;
+
+typedef struct mst_clip_weights {
+    int32_t layers, vocab, context, width, heads, ffn;
+    const void* tok_emb_dev;
+    const void* pos_emb_dev;
+    const float* lnf_g_dev;
+    const float* lnf_b_dev;
+    const void* proj_dev;
+    const mst_clip_layer* layer_host; /* host array of `layers` entries */
+} mst_clip_weights;
+
+int mst_clip_pack_weight(const void* src_dev, int32_t src_is_f16, int32_t n, int32_t k, void* dst_dev, void* stream);
+int mst_clip_plan(const int32_t* lens_host, int32_t batch, int32_t context, int32_t* offsets_host, int32_t* total_rows,
+                  int64_t* workspace_bytes);
+int mst_clip_encode(const mst_clip_weights* w, const int32_t* ids_dev, int32_t batch, int32_t ids_stride, const int32_t* lens_dev,
+                    const int32_t* offsets_dev, int32_t total_rows, void* workspace_dev, int64_t workspace_bytes, float* out_dev,
+                    void* stream);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
