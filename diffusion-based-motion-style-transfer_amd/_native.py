@@ -180,6 +180,19 @@ SIGNATURES = {
                                 C.POINTER(C.c_int64)]),
     "mst_clip_encode": (C.c_int, [C.POINTER(MstClipWeights), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mst_smpl_packed_bytes": (C.c_int64, [C.c_int32]),
+    "mst_smpl_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "mst_smpl_pack_body": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mst_smpl_pose": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p,
+                                C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
+    "mst_smpl_skin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                C.c_int64, C.c_void_p]),
+    "mst_smpl_regress": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                   C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                   C.c_void_p]),
     "mst_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "mst_profile_event_overhead_us": (C.c_float, [C.c_void_p]),
     "mst_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(C.c_int32),

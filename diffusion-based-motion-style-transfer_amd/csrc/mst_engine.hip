@@ -40,6 +40,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_plan.h"
 #include "mst_vb.h"
 #include "mst_clip.h"
+#include "mst_smpl.h"
 
 using namespace mst;
 
@@ -3826,6 +3827,124 @@ extern "C" int mst_rot_decode(const float* data, int64_t stride_batch, int64_t s
     p.local = local_rows;
     const size_t lds = route == kRotPosIk ? sizeof(float) * 2 * frames : 0;      // at most 32 KB: below the opt-in threshold
     hipLaunchKernelGGL(k_rot_decode, dim3(batch), dim3(kRotThreads), lds, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ the SMPL body (mst_smpl.h)
+static int smpl_counts(const char* who, int32_t live, int32_t vertices) {
+    if (vertices <= 0) return fail("%s: %d vertices", who, vertices);
+    if (live < 1) return fail("%s: %d live frames", who, live);
+    if ((int64_t)live * vertices * 3 >= ((int64_t)1 << 40)) return fail("%s: %d frames x %d vertices is beyond any device", who, live, vertices);
+    return 0;
+}
+extern "C" int64_t mst_smpl_packed_bytes(int32_t vertices) {
+    if (vertices <= 0) {
+        fail("mst_smpl_packed_bytes: %d vertices", vertices);
+        return -1;
+    }
+    return (int64_t)((vertices + kSmplTileV - 1) / kSmplTileV) * kSmplTileFloats * 4;
+}
+extern "C" int64_t mst_smpl_workspace_bytes(int32_t live, int32_t vertices, int32_t keep_vertices) {
+    if (smpl_counts("mst_smpl_workspace_bytes", live, vertices)) return -1;
+    return smpl_carve(nullptr, live, vertices, keep_vertices != 0).bytes;
+}
+extern "C" int mst_smpl_pack_body(const float* posedirs, const float* shapedirs, int32_t vertices, float* packed, void* stream) {
+    if (vertices <= 0) return fail("mst_smpl_pack_body: %d vertices", vertices);
+    if (!posedirs || !shapedirs || !packed) return fail("mst_smpl_pack_body: null posedirs, shapedirs or destination");
+    const int64_t total = mst_smpl_packed_bytes(vertices) / 4;
+    hipLaunchKernelGGL(k_smpl_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, posedirs, shapedirs, packed, vertices, total);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+extern "C" int mst_smpl_pose(const float* x, int64_t stride_batch, int64_t stride_joint, int64_t stride_feat, int64_t stride_frame,
+                             const int32_t* frame_ids, int32_t live, int32_t batch, int32_t frames, int32_t sample_joints, int32_t joints,
+                             int32_t vertices, int32_t keep_vertices, int32_t pose_rep, int32_t glob, const float* glob_rot, const float* betas, float beta, const float* j0,
+                             const float* jdirs, const int32_t* parents, int32_t trans_joint, void* workspace, float* rotations,
+                             float* joints_out, void* stream) {
+    if (joints != kSmplJoints) return fail("mst_smpl_pose: a body of %d joints; only SMPL's %d are built", joints, kSmplJoints);
+    if (!x || !j0 || !jdirs || !parents || !workspace) return fail("mst_smpl_pose: null sample, joint tables, parents or workspace");
+    CHECK(smpl_counts("mst_smpl_pose", live, vertices));
+    if (batch < 1 || frames < 1 || (int64_t)batch * frames > INT32_MAX) return fail("mst_smpl_pose: %d clips of %d frames", batch, frames);
+    if (!frame_ids && (batch != 1 || live != frames)) return fail("mst_smpl_pose: without frame ids every frame of ONE clip is live (batch %d, live %d, frames %d)", batch, live, frames);
+    if (live > (int64_t)batch * frames) return fail("mst_smpl_pose: %d live frames in %d clips of %d", live, batch, frames);
+    if (pose_rep < kSmplRot6d || pose_rep > kSmplRotvec) return fail("mst_smpl_pose: pose_rep %d is none of 0 (rot6d), 1 (rotmat), 2 (rotquat), 3 (rotvec)", pose_rep);
+    const int need = glob ? kSmplJoints : kSmplJoints - 1;
+    if (sample_joints < need) return fail("mst_smpl_pose: the sample has %d rotation rows, %d are read (glob %d)", sample_joints, need, glob != 0);
+    if (!glob && !glob_rot) return fail("mst_smpl_pose: glob = 0 needs the global rotation");
+    if (trans_joint >= 0 && !joints_out) return fail("mst_smpl_pose: a translation row without a joints output");
+    if (parents[0] != -1) return fail("mst_smpl_pose: parents[0] = %d, the root's is -1", parents[0]);
+    SmplPoseArgs p{};
+    for (int j = 1; j < kSmplJoints; j++) {
+        if (parents[j] < 0 || parents[j] >= j) return fail("mst_smpl_pose: parents[%d] = %d is not an earlier joint", j, parents[j]);
+        p.parents[j] = (signed char)parents[j];
+    }
+    p.parents[0] = -1;
+    const SmplWorkspace ws = smpl_carve(workspace, live, vertices, keep_vertices != 0);
+    p.x = x; p.sb = stride_batch; p.sj = stride_joint; p.sf = stride_feat; p.st = stride_frame;
+    p.frame_ids = frame_ids; p.N = live; p.B = batch; p.T = frames; p.rep = pose_rep; p.glob = glob != 0;
+    if (glob_rot)
+        for (int c = 0; c < 3; c++) p.glob_rot[c] = glob_rot[c];
+    p.betas = betas; p.beta = beta; p.J0 = j0; p.Jdirs = jdirs; p.trans_joint = trans_joint;
+    p.A = ws.A; p.rows = ws.rows; p.posed = ws.posed; p.rot = rotations; p.out = joints_out;
+    hipLaunchKernelGGL(k_smpl_pose, dim3((live + 63) / 64), dim3(64), 0, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+extern "C" int mst_smpl_skin(const float* packed, const float* v_template, const float* weights, int32_t vertices, int32_t keep_vertices, const int32_t* frame_ids,
+                             int32_t live, int32_t batch, int32_t frames, void* workspace, const float* trans, int64_t trans_stride_batch,
+                             int64_t trans_stride_axis, int64_t trans_stride_frame, float* out, int64_t out_stride_batch, int64_t out_stride_frame,
+                             int64_t out_stride_vertex, int64_t out_stride_axis, void* stream) {
+    if (!packed || !v_template || !weights || !workspace) return fail("mst_smpl_skin: null body arrays or workspace");
+    CHECK(smpl_counts("mst_smpl_skin", live, vertices));
+    if (batch < 1 || frames < 1 || (int64_t)batch * frames > INT32_MAX) return fail("mst_smpl_skin: %d clips of %d frames", batch, frames);
+    if (!out && !keep_vertices) return fail("mst_smpl_skin: no output: neither a destination nor the workspace's vertices");
+    if (out && !frame_ids && (batch != 1 || live != frames)) return fail("mst_smpl_skin: without frame ids every frame of ONE clip is live");
+    if (!out && trans) return fail("mst_smpl_skin: the workspace's vertices carry no translation");
+    const SmplWorkspace ws = smpl_carve(workspace, live, vertices, keep_vertices != 0);
+    SmplSkinArgs p{};
+    p.packed = packed; p.v_template = v_template; p.weights = weights; p.A = ws.A; p.rows = ws.rows;
+    p.N = live; p.V = vertices; p.T = frames; p.B = batch;
+    if (out) {
+        p.frame_ids = frame_ids; p.trans = trans; p.tb = trans_stride_batch; p.tc = trans_stride_axis; p.tt = trans_stride_frame;
+        p.out = out; p.ob = out_stride_batch; p.ot = out_stride_frame; p.ov = out_stride_vertex; p.oc = out_stride_axis;
+    } else {                                 // [N][V][3] for k_smpl_regress: frame n as frame n of one clip
+        p.frame_ids = nullptr; p.B = 1; p.T = live;
+        p.out = ws.verts; p.ob = 0; p.ot = (int64_t)vertices * 3; p.ov = 3; p.oc = 1;
+    }
+    CHECK(ensure_dyn_lds((const void*)k_smpl_skin, kSmplTileFloats * 4));
+    // frame tiles are dealt to 8 waves x `split` workgroups a vertex tile: enough workgroups to cover the chip when the body is small.
+    // A tile's arithmetic does not depend on which wave runs it.
+    const int vt = (vertices + kSmplTileV - 1) / kSmplTileV, ft = (live + 15) / 16, per = kSmplSkinThreads / 64;
+    const int split = std::max(1, std::min((ft + per - 1) / per, (512 + vt - 1) / vt));
+    hipLaunchKernelGGL(k_smpl_skin, dim3(vt, split), dim3(kSmplSkinThreads), kSmplTileFloats * 4, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+extern "C" int mst_smpl_regress(void* workspace, const float* extra, const int32_t* vertex_ids, int32_t vertices, const int32_t* frame_ids,
+                                int32_t live, int32_t batch, int32_t frames, const int32_t* map, int32_t map_len, int32_t root,
+                                const float* trans, int64_t trans_stride_batch, int64_t trans_stride_axis, int64_t trans_stride_frame,
+                                float* out, void* stream) {
+    if (!workspace || !extra || !vertex_ids || !map || !out) return fail("mst_smpl_regress: null workspace, regressor, vertex ids, joint map or output");
+    CHECK(smpl_counts("mst_smpl_regress", live, vertices));
+    if (batch < 1 || frames < 1 || (int64_t)batch * frames > INT32_MAX) return fail("mst_smpl_regress: %d clips of %d frames", batch, frames);
+    if (!frame_ids && (batch != 1 || live != frames)) return fail("mst_smpl_regress: without frame ids every frame of ONE clip is live");
+    if (map_len < 1 || map_len > kSmplAllJoints) return fail("mst_smpl_regress: a list of %d joints outside 1..%d", map_len, kSmplAllJoints);
+    if (root < -1 || root >= map_len) return fail("mst_smpl_regress: root %d outside the list of %d (-1: none subtracted)", root, map_len);
+    SmplRegressArgs p{};
+    for (int i = 0; i < kSmplVertexIds; i++) {
+        if (vertex_ids[i] < 0 || vertex_ids[i] >= vertices) return fail("mst_smpl_regress: vertex id %d outside 0..%d", vertex_ids[i], vertices - 1);
+        p.vertex_ids[i] = vertex_ids[i];
+    }
+    for (int i = 0; i < map_len; i++) {
+        if (map[i] < 0 || map[i] >= kSmplAllJoints) return fail("mst_smpl_regress: map[%d] = %d outside 0..%d", i, map[i], kSmplAllJoints - 1);
+        p.map[i] = map[i];
+    }
+    const SmplWorkspace ws = smpl_carve(workspace, live, vertices, true);
+    p.verts = ws.verts; p.posed = ws.posed; p.extra = extra; p.frame_ids = frame_ids; p.N = live; p.V = vertices; p.T = frames; p.B = batch;
+    p.map_len = map_len; p.root = root; p.trans = trans; p.tb = trans_stride_batch; p.tc = trans_stride_axis; p.tt = trans_stride_frame;
+    p.out = out;
+    hipLaunchKernelGGL(k_smpl_regress, dim3(live), dim3(256), 0, (hipStream_t)stream, p);
     HIPCHECK(hipGetLastError());
     return 0;
 }

@@ -362,6 +362,14 @@ class MDM(nn.Module, _EngineHost):
         self.set_text_encoder(enc)
         return enc
 
+    def use_smpl_body(self, body):
+        """`self.rot2xyz` on the GPU with this package alone (model/rotation2xyz.py): `body` a `model.smpl.SMPLBody` -- the user's
+        SMPL file, nothing is bundled.  The reference builds it in its constructor (model/mdm_forstyledataset.py:270); without this
+        call `rot2xyz` stays None.  Returns the Rotation2xyz it set."""
+        from .rotation2xyz import Rotation2xyz
+        self.rot2xyz = Rotation2xyz(next(self.parameters()).device, dataset=self.dataset, body=body)
+        return self.rot2xyz
+
     def mask_cond(self, cond, force_mask=False):
         return _mask_cond(self, cond, force_mask)
 
@@ -540,6 +548,12 @@ class StyleDiffusion(nn.Module, _EngineHost):
 
     def parameters_wo_enc(self):
         return [p for name, p in self.named_parameters() if not name.startswith('motion_enc.')]
+
+    def use_smpl_body(self, body):
+        """The frozen prior's `MDM.use_smpl_body`, also reachable as `self.rot2xyz` (what ClassifierFreeSampleModel and StyleBank
+        pick up)."""
+        self.rot2xyz = self._prior().use_smpl_body(body)
+        return self.rot2xyz
 
     def mask_cond(self, cond, force_mask=False):
         return _mask_cond(self, cond, force_mask)

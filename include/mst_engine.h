@@ -887,6 +887,60 @@ int mst_clip_encode(const mst_clip_weights* w, const int32_t* ids_dev, int32_t b
                     const int32_t* offsets_dev, int32_t total_rows, void* workspace_dev, int64_t workspace_bytes, float* out_dev,
                     void* stream);
 
+/* -----------------------------------------------------------------------------------------
+ * The SMPL body (csrc/mst_smpl.h), forward only, fp32.  Replaces: smplx.SMPLLayer's forward (`lbs`) under model/smpl.py:86-97 and the
+ * conversions, masking, root subtraction and translation of model/rotation2xyz.py:17-92 (Rotation2xyz.__call__), called by
+ * visualize/vis_utils.py:37 and visualize/render_final.py:62.  Stateless: every pointer but the `_host` ones is a device pointer,
+ * every launch goes to `stream`, nothing is allocated and nothing synchronises.  No atomics, no split-K: a frame's output is a
+ * fixed-order sum of its own operands and depends on neither the batch, its position in it, other clips' lengths nor the stream.
+ * Only bodies of 24 joints are built.
+ *
+ * mst_smpl_packed_bytes / mst_smpl_pack_body: posedirs [207][3 vertices] (row k = 9 (joint - 1) + 3 row + column of R - I, column
+ * 3 vertex + axis) and shapedirs [vertices][3][10] -> the operand image mst_smpl_skin streams: per tile of 32 vertices 224 rows
+ * (207 pose rows, 10 shape rows, 7 zeros) x 96 columns in MFMA fragment order.  Once per body.
+ * mst_smpl_workspace_bytes: what one call chain (pose -> skin -> regress) needs for `live` frames; keep_vertices != 0 adds the
+ * [live][vertices][3] vertices mst_smpl_regress reads.  The three entries carve it alike from (live, vertices, keep_vertices).
+ * mst_smpl_pose (rotation2xyz.py:38-66 and lbs' joints): element (b, j, f, t) of the sample at x_dev[b * stride_batch + j * stride_joint +
+ * f * stride_feat + t * stride_frame], read where it lies.  frame_ids_dev [live]: b * frames + t of every live frame in ascending
+ * order (values are clamped into the sample), or NULL when batch = 1 and every frame is live.  pose_rep 0 rot6d (6 features; the
+ * reference's own column form, utils/rotation_conversions.py:536-551, no epsilon), 1 rotmat (9), 2 rotquat (4; :38-66), 3 rotvec (3;
+ * :448-478 with its branch at 1e-6).  glob != 0: sample row 0 is the global orientation and rows 1 .. 23 the body pose; glob = 0:
+ * glob_rot_host[3], one axis-angle for every frame, and sample rows 0 .. 22.  betas_dev [live][10], or NULL for (0, beta, 0, ...).
+ * j0_dev [24][3] and jdirs_dev [24][3][10]: J_regressor (v_template + shapedirs beta) split into its constant and its linear part (the
+ * host forms them in double).  parents_host[24]: parents[0] = -1, parents[j] < j.  Writes the workspace (the transforms A [live][24][12],
+ * the operand rows [live][224], the posed joints [live][24][3]); rotations_dev [live][24][3][3] (optional): the matrices;
+ * joints_out_dev [batch][24][3][frames] (optional; jointstype 'smpl'): the posed joints minus joint 0, plus trans[t] - trans[0] when
+ * trans_joint >= 0 names the sample row whose features 0 .. 2 are the translation.  Frames that are not live are not written.
+ * mst_smpl_skin (lbs' vertices): v_posed = v_template + [R - I, beta] [posedirs; shapedirs], T[v] = sum_j W[v][j] A[j] over all 24
+ * joints in ascending order, vertex = T [v_posed; 1], + trans[t] - trans[0] when trans_dev is given (element (b, axis, t) at
+ * trans_dev[b * trans_stride_batch + axis * trans_stride_axis + t * trans_stride_frame]).  Element (b, t, v, axis) goes to
+ * out_dev[b * out_stride_batch + t * out_stride_frame + v * out_stride_vertex + axis * out_stride_axis]: the reference's
+ * [batch][vertices][3][frames] and a [batch][frames][vertices][3] sequence layout are the same store.  out_dev = NULL: into the
+ * workspace's vertices, for mst_smpl_regress.  weights_dev [vertices][24], v_template_dev [vertices][3].
+ * mst_smpl_regress (smpl.py:89-95): the list of 54 = 24 posed joints | the vertices at vertex_ids_host[21] | extra_dev [9][vertices]
+ * times the vertices (summed in double, fixed order); output joint i is entry map_host[i], minus entry map_host[root] (root = -1:
+ * nothing subtracted), plus the translation -> out_dev [batch][map_len][3][frames].
+ * Refused without touching a device: null pointers, vertices <= 0, live < 1, joints != 24, parents[0] != -1 or a parents entry that is
+ * not an earlier joint, a pose_rep outside 0 .. 3, a sample with too few rotation rows, a vertex id outside the body, a map entry outside
+ * 0 .. 53, a root outside the list, a missing frame-id list when more than one clip or not every frame is live.
+ * ----------------------------------------------------------------------------------------- */
+int64_t mst_smpl_packed_bytes(int32_t vertices);
+int64_t mst_smpl_workspace_bytes(int32_t live, int32_t vertices, int32_t keep_vertices);
+int mst_smpl_pack_body(const float* posedirs_dev, const float* shapedirs_dev, int32_t vertices, float* packed_dev, void* stream);
+int mst_smpl_pose(const float* x_dev, int64_t stride_batch, int64_t stride_joint, int64_t stride_feat, int64_t stride_frame,
+                  const int32_t* frame_ids_dev, int32_t live, int32_t batch, int32_t frames, int32_t sample_joints, int32_t joints,
+                  int32_t vertices, int32_t keep_vertices, int32_t pose_rep, int32_t glob, const float* glob_rot_host,
+                  const float* betas_dev, float beta, const float* j0_dev, const float* jdirs_dev, const int32_t* parents_host,
+                  int32_t trans_joint, void* workspace_dev, float* rotations_dev, float* joints_out_dev, void* stream);
+int mst_smpl_skin(const float* packed_dev, const float* v_template_dev, const float* weights_dev, int32_t vertices, int32_t keep_vertices,
+                  const int32_t* frame_ids_dev, int32_t live, int32_t batch, int32_t frames, void* workspace_dev, const float* trans_dev,
+                  int64_t trans_stride_batch, int64_t trans_stride_axis, int64_t trans_stride_frame, float* out_dev,
+                  int64_t out_stride_batch, int64_t out_stride_frame, int64_t out_stride_vertex, int64_t out_stride_axis, void* stream);
+int mst_smpl_regress(void* workspace_dev, const float* extra_dev, const int32_t* vertex_ids_host, int32_t vertices,
+                     const int32_t* frame_ids_dev, int32_t live, int32_t batch, int32_t frames, const int32_t* map_host, int32_t map_len,
+                     int32_t root, const float* trans_dev, int64_t trans_stride_batch, int64_t trans_stride_axis,
+                     int64_t trans_stride_frame, float* out_dev, void* stream);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
