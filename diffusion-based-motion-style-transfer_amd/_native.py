@@ -39,6 +39,10 @@ class MstGuideArgs(C.Structure):
                 ("mask_dev", C.c_void_p), ("weight_dev", C.c_void_p)]
 
 
+class MstSmplifyWeights(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("sigma", "joint", "prior", "angle", "shape", "keep", "depth")]
+
+
 class MstClipLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "ln1_g", "ln1_b", "wqkv", "bqkv", "wo", "bo", "ln2_g", "ln2_b", "w1", "b1", "w2", "b2")]
@@ -193,6 +197,13 @@ SIGNATURES = {
     "mst_smpl_regress": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                    C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                    C.c_void_p]),
+    "mst_smplify_packed_prior_bytes": (C.c_int64, []),
+    "mst_smplify_pack_prior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mst_smplify_workspace_bytes": (C.c_int64, [C.c_int32]),
+    "mst_smplify_objective": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
+                                        C.POINTER(MstSmplifyWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "mst_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "mst_profile_event_overhead_us": (C.c_float, [C.c_void_p]),
     "mst_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(C.c_int32),

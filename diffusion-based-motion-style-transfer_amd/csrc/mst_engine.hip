@@ -41,6 +41,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_vb.h"
 #include "mst_clip.h"
 #include "mst_smpl.h"
+#include "mst_smplify.h"
 
 using namespace mst;
 
@@ -3946,6 +3947,59 @@ extern "C" int mst_smpl_regress(void* workspace, const float* extra, const int32
     p.out = out;
     hipLaunchKernelGGL(k_smpl_regress, dim3(live), dim3(256), 0, (hipStream_t)stream, p);
     HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ the SMPLify-3D objective (mst_smplify.h)
+extern "C" int64_t mst_smplify_packed_prior_bytes(void) { return (int64_t)kFitPackedFloats * 4; }
+extern "C" int mst_smplify_pack_prior(const float* precisions, const float* means, const float* neg_log_weights, void* packed, void* stream) {
+    if (!precisions || !means || !neg_log_weights || !packed) return fail("mst_smplify_pack_prior: null precisions, means, constants or destination");
+    hipLaunchKernelGGL(k_smplify_pack, dim3((kFitPackedFloats + 255) / 256), dim3(256), 0, (hipStream_t)stream, precisions, means, neg_log_weights, (float*)packed);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+extern "C" int64_t mst_smplify_workspace_bytes(int32_t frames) {
+    if (frames < 1) {
+        fail("mst_smplify_workspace_bytes: %d frames", frames);
+        return -1;
+    }
+    return ((int64_t)frames * kFitJoints * 3 * 4 + 255) / 256 * 256;
+}
+extern "C" int mst_smplify_objective(int32_t stage, int32_t nj, int32_t frames, const float* body_pose, const float* global_orient, const float* betas,
+                                     const float* camera_translation, const float* target, const float* conf, const float* preserve,
+                                     const float* camera_estimate, const float* j0, const float* jdirs, const int32_t* parents,
+                                     const void* packed_prior, const mst_smplify_weights* weights, void* workspace, float* per_frame,
+                                     float* loss, float* grad_body_pose, float* grad_global_orient, float* grad_betas,
+                                     float* grad_camera_translation, float* rotations, void* stream) {
+    if (stage != kFitCamera && stage != kFitBody) return fail("mst_smplify_objective: stage %d is neither 0 (camera) nor 1 (body)", stage);
+    if (nj != 22 && nj != kFitJoints) return fail("mst_smplify_objective: %d target joints; 22 (AMASS) or 24 (orig)", nj);
+    if (frames < 1) return fail("mst_smplify_objective: %d frames", frames);
+    if (!body_pose || !global_orient || !betas || !camera_translation || !target || !j0 || !jdirs || !parents || !weights || !workspace || !per_frame)
+        return fail("mst_smplify_objective: null pose, orientation, betas, camera translation, target, joint tables, parents, weights, workspace or per-frame loss");
+    if (stage == kFitBody && (!conf || !preserve || !packed_prior)) return fail("mst_smplify_objective: the body stage needs the confidences, the preserved pose and the packed prior");
+    if (stage == kFitCamera && !camera_estimate) return fail("mst_smplify_objective: the camera stage needs the camera estimate");
+    if (stage == kFitCamera && (grad_body_pose || grad_betas)) return fail("mst_smplify_objective: the camera stage has no body-pose or betas gradient");
+    if (parents[0] != -1) return fail("mst_smplify_objective: parents[0] = %d, the root's is -1", parents[0]);
+    FitArgs p{};
+    for (int j = 1; j < kFitJoints; j++) {
+        if (parents[j] < 0 || parents[j] >= j) return fail("mst_smplify_objective: parents[%d] = %d is not an earlier joint", j, parents[j]);
+        p.parents[j] = (signed char)parents[j];
+    }
+    p.parents[0] = -1;
+    p.stage = stage; p.nj = nj; p.N = frames; p.pose = body_pose; p.orient = global_orient; p.betas = betas; p.cam = camera_translation;
+    p.target = target; p.conf = conf; p.preserve = preserve; p.cam_est = camera_estimate; p.J0 = j0; p.Jdirs = jdirs;
+    p.packed = (const float*)packed_prior;
+    p.sel[0] = 2; p.sel[1] = 1; p.sel[2] = 17; p.sel[3] = 16;       // RHip, LHip, RShoulder, LShoulder in both joint categories
+    p.sigma = weights->sigma; p.w_joint = weights->joint; p.w_prior = weights->prior; p.w_angle = weights->angle; p.w_shape = weights->shape;
+    p.w_keep = weights->keep; p.w_depth = weights->depth;
+    p.per_frame = per_frame; p.joints = (float*)workspace; p.g_pose = grad_body_pose; p.g_orient = grad_global_orient; p.g_betas = grad_betas;
+    p.g_cam = grad_camera_translation; p.rot = rotations;
+    hipLaunchKernelGGL(k_smplify, dim3((frames + kFitFrames - 1) / kFitFrames), dim3(64), 0, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    if (loss) {
+        hipLaunchKernelGGL(k_smplify_sum, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)per_frame, frames, loss);
+        HIPCHECK(hipGetLastError());
+    }
     return 0;
 }
 

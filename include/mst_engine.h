@@ -941,6 +941,50 @@ int mst_smpl_regress(void* workspace_dev, const float* extra_dev, const int32_t*
                      int32_t root, const float* trans_dev, int64_t trans_stride_batch, int64_t trans_stride_axis,
                      int64_t trans_stride_frame, float* out_dev, void* stream);
 
+/* -----------------------------------------------------------------------------------------
+ * The SMPLify-3D objective (csrc/mst_smplify.h): value and gradient of one stage of the fit for every frame of a clip, fp32, the
+ * reverse pass written by hand.  Replaces, per evaluation of an optimiser's closure: the smplx forward pass, camera_fitting_loss_3d and
+ * body_fitting_loss_3d (visualize/joints2smpl/src/customloss.py:6-21, :128-226), MaxMixturePrior.merged_log_likelihood
+ * (prior.py:180-195) and `loss.backward()` (smplify.py:168-181, :218-235, :260-272).  No vertex is formed: the posed joints are
+ * J0 + Jdirs beta through the rigid chain.  Stateless: every pointer but the `_host` ones is a device pointer, every launch goes to
+ * `stream`, nothing is allocated and nothing synchronises; at most two launches.  No atomics, no split-K: a frame's loss and gradients
+ * are the same bits alone, anywhere in a batch and on any stream, whatever other frames hold.
+ *
+ * mst_smplify_packed_prior_bytes / mst_smplify_pack_prior: precisions_dev [8][69][69] -- the SYMMETRIC part 1/2 (P + P^T) of the
+ * float32 precisions, formed by the host in double -- means_dev [8][69] and neg_log_weights_dev [8] = -log(nll_weights) -> the operand
+ * image of the kernel (precisions in MFMA fragment order, K = 69 padded to 72, five 16-row tiles).  Once per prior.
+ * mst_smplify_workspace_bytes: [frames][24][3] floats, 256-byte aligned.  After a call the workspace holds the posed joints (no camera
+ * translation) of every frame: what guess_init_3d (smplify.py:19-40) reads.
+ * mst_smplify_objective: stage 0 (camera): sum over the joints 2, 1, 17, 16 of |target - (joint + cam)|^2 + depth^2 |cam - cam_est|^2;
+ * gradients to global_orient and camera_translation only.  The reference's broadcast adds its depth term once per selected joint
+ * (customloss.py:219-226): the caller states that as depth = 2 x 100.  stage 1 (body): joint^2 sum_j conf_j^2 sum_c gmof(joint + cam -
+ * target, sigma) + prior^2 min_m [1/2 d_m^T P_m d_m - log nll_weight_m] + angle^2 sum exp(s_i pose[i])^2 over entries 52, 55, 9, 12
+ * (signs +, -, -, -) + shape^2 |betas|^2 + keep^2 |body_pose - preserve|^2; the smallest component wins, ties to the lowest index.
+ * body_pose_dev [frames][69], global_orient_dev [frames][3], betas_dev [frames][10], camera_translation_dev [frames][3], target_dev
+ * [frames][nj][3] with nj = 22 ('AMASS') or 24 ('orig'), conf_dev [nj], preserve_dev [frames][69], camera_estimate_dev [frames][3],
+ * j0_dev [24][3], jdirs_dev [24][3][10], parents_host[24].  Rotations are smplx's batch_rodrigues form as recalled (not verified, see
+ * csrc/mst_smplify.h): |theta + 1e-8|, K = skew(theta / angle), I + sin K + (1 - cos) K K.  Outputs: per_frame_dev [frames]; loss_dev [1]
+ * (optional): their sum in double in ascending frame order, rounded once; grad_*_dev in the operands' layouts, each optional (NULL: not
+ * computed and nothing written); rotations_dev [frames][24][3][3] (optional).
+ * Refused without touching a device: null operands, frames < 1, nj not 22 or 24, a stage outside 0 .. 1, the stage's own operands
+ * missing, a body-pose or betas gradient asked of the camera stage, parents[0] != -1 or a parents entry that is not an earlier joint.
+ * ----------------------------------------------------------------------------------------- */
+typedef struct mst_smplify_weights {
+    float sigma, joint, prior, angle, shape, keep, depth;
+} mst_smplify_weights;
+
+int64_t mst_smplify_packed_prior_bytes(void);
+int mst_smplify_pack_prior(const float* precisions_dev, const float* means_dev, const float* neg_log_weights_dev, void* packed_dev,
+                           void* stream);
+int64_t mst_smplify_workspace_bytes(int32_t frames);
+int mst_smplify_objective(int32_t stage, int32_t nj, int32_t frames, const float* body_pose_dev, const float* global_orient_dev,
+                          const float* betas_dev, const float* camera_translation_dev, const float* target_dev, const float* conf_dev,
+                          const float* preserve_dev, const float* camera_estimate_dev, const float* j0_dev, const float* jdirs_dev,
+                          const int32_t* parents_host, const void* packed_prior_dev, const mst_smplify_weights* weights_host,
+                          void* workspace_dev, float* per_frame_dev, float* loss_dev, float* grad_body_pose_dev,
+                          float* grad_global_orient_dev, float* grad_betas_dev, float* grad_camera_translation_dev, float* rotations_dev,
+                          void* stream);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
