@@ -2054,12 +2054,18 @@ static int guide_check(const char* who, const mst_schedule* s, int sampler, cons
     return 0;
 }
 
+// The guide of a whole loop (mst_sample_loop_guided, mst_window_sample_loop): guide_check, and a caller's gradient belongs to one step.
+static int loop_guide_check(const char* who, const mst_schedule* s, const mst_loop_args* a, const mst_guide_args* g) {
+    CHECK(guide_check(who, s, a->sampler, g));
+    if (g->kind == MST_GUIDE_GRADIENT && a->t_start != a->t_end)
+        return fail("%s: MST_GUIDE_GRADIENT carries the gradient of ONE step: t_start %d must equal t_end %d", who, a->t_start, a->t_end);
+    return 0;
+}
+
 // p_sample_loop / ddim_sample_loop with a cond_fn (gaussian_diffusion.py:644-794 / :948-1082 with :577-580 / :821-824).
 extern "C" int mst_sample_loop_guided(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_guide_args* g, void* stream) {
     if (!s || !a || !g) return fail("mst_sample_loop_guided: null argument");
-    CHECK(guide_check("mst_sample_loop_guided", s, a->sampler, g));
-    if (g->kind == MST_GUIDE_GRADIENT && a->t_start != a->t_end)
-        return fail("mst_sample_loop_guided: MST_GUIDE_GRADIENT carries the gradient of ONE step: t_start %d must equal t_end %d", a->t_start, a->t_end);
+    CHECK(loop_guide_check("mst_sample_loop_guided", s, a, g));
     return sample_loop_run(e, s, a, nullptr, stream, g);
 }
 
@@ -2190,16 +2196,23 @@ extern "C" int mst_window_stitch(const mst_window_plan* p, float* win_dev, int32
     return window_stitch_launch(p, win_dev, feats, long_out_dev, (hipStream_t)stream);
 }
 
-// ddim_sample_loop over every window of every long clip as ONE batch, stitched behind every step (sample_loop_run with a plan).
+// What both windowed loops ask of their plan: the loop's batch is the plan's windows, on the engine's device.
+static int window_plan_check(const char* who, const mst_engine* e, const mst_loop_args* a, const mst_window_plan* p) {
+    if (a->batch != p->windows) return fail("%s: batch %d is not the plan's window count %d", who, a->batch, p->windows);
+    if (a->frames != p->window) return fail("%s: frames %d is not the plan's window %d", who, a->frames, p->window);
+    if (p->device != e->cfg.device) return fail("%s: the plan lives on device %d, the engine on device %d", who, p->device, e->cfg.device);
+    return 0;
+}
+
+// ddim_sample_loop over every window of every long clip as ONE batch, stitched behind every step (sample_loop_run with a plan): the
+// deterministic subset of mst_window_sample_loop over the same code, with its own two refusals in front.
 extern "C" int mst_sample_loop_windows(mst_engine* e, const mst_schedule* s, const mst_loop_args* a, const mst_window_plan* p, void* stream) {
     const char* who = "mst_sample_loop_windows";
     if (!e || !s || !a || !p) return fail("%s: null argument", who);
     if (a->sampler != MST_SAMPLER_DDIM)
         return fail("%s: sampler %d is not MST_SAMPLER_DDIM: only the deterministic DDIM step keeps the windows' shared frames identical", who, a->sampler);
     if (a->eta != 0.0f) return fail("%s: eta %g must be 0: a stochastic step would need per-window noise unfolded from one long draw", who, (double)a->eta);
-    if (a->batch != p->windows) return fail("%s: batch %d is not the plan's window count %d", who, a->batch, p->windows);
-    if (a->frames != p->window) return fail("%s: frames %d is not the plan's window %d", who, a->frames, p->window);
-    if (p->device != e->cfg.device) return fail("%s: the plan lives on device %d, the engine on device %d", who, p->device, e->cfg.device);
+    CHECK(window_plan_check(who, e, a, p));
     return sample_loop_run(e, s, a, nullptr, stream, nullptr, p);
 }
 
@@ -2238,14 +2251,8 @@ extern "C" int mst_window_sample_loop(mst_engine* e, const mst_schedule* s, cons
                         "would draw different numbers for it; fill a buffer with mst_window_noise and pass MST_NOISE_BUFFER", who);
         if (!a->noise_dev) return fail("%s: noise buffer missing (mst_window_noise fills one)", who);
     }
-    if (a->batch != p->windows) return fail("%s: batch %d is not the plan's window count %d", who, a->batch, p->windows);
-    if (a->frames != p->window) return fail("%s: frames %d is not the plan's window %d", who, a->frames, p->window);
-    if (p->device != e->cfg.device) return fail("%s: the plan lives on device %d, the engine on device %d", who, p->device, e->cfg.device);
-    if (g) {
-        CHECK(guide_check(who, s, a->sampler, g));
-        if (g->kind == MST_GUIDE_GRADIENT && a->t_start != a->t_end)
-            return fail("%s: MST_GUIDE_GRADIENT carries the gradient of ONE step: t_start %d must equal t_end %d", who, a->t_start, a->t_end);
-    }
+    CHECK(window_plan_check(who, e, a, p));
+    if (g) CHECK(loop_guide_check(who, s, a, g));
     return sample_loop_run(e, s, a, nullptr, stream, g, p);
 }
 

@@ -105,6 +105,15 @@ def _refuse_bank(model, what):
         raise RuntimeError(f"{what}: a StyleBank does not run under autograd; fine-tune each StyleDiffusion on its own")
 
 
+def _plms_refuse(order, cond_fn, denoised_fn):
+    """What plms_sample and every PLMS loop entry refuse in front of their own work: a bad order, a cond_fn, a denoised_fn."""
+    if not int(order) or not 1 <= order <= 4:
+        raise ValueError('order is invalid (should be int from 1-4).')
+    if cond_fn is not None or denoised_fn is not None:
+        raise NotImplementedError("plms_sample: cond_fn / denoised_fn are not built for the PLMS sampler (guided PLMS is out of scope); "
+                                  "p_sample, ddim_sample and their loops take them")
+
+
 def vb_row_plan(n_clips, num_timesteps, rows=None):
     """The (clip, timestep) rows of `calc_bpd_loop` as chunks [(clip indices, timestep indices)] of at most `rows` rows each: timestep
     DESCENDING (the reference's visiting order, :1571) and, inside a timestep, clip ascending, so the concatenated results view as
@@ -570,6 +579,35 @@ class GaussianDiffusion:
                                  "ORIGINAL process's table (the one its timesteps index)")
         return _eng.guide_args(x, target=cond_fn.target, mask=cond_fn.mask, weight=cond_fn.weight, follow_schedule=follow)
 
+    def _chunk_size(self, x, nsteps, buffer, dump):
+        """Indices per native call of an `nsteps` loop on `x`: with a noise buffer at most `noise_chunk` and what keeps the
+        [steps, B, F, 1, T] buffer within `noise_chunk_bytes`; with an x0-hat dump alone the dump is bounded the same way; with
+        neither the whole loop is one call."""
+        bound = max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
+        if buffer:
+            return max(1, min(int(self.noise_chunk), bound))
+        return bound if dump else nsteps
+
+    @staticmethod
+    def _chunks(indices, chunk, progress):
+        """(c0, indices[c0:c0 + chunk], whether it is the last) for every chunk of a native loop, under tqdm when `progress`."""
+        it = range(0, len(indices), chunk)
+        if progress:
+            from tqdm.auto import tqdm
+            it = tqdm(it)
+        for c0 in it:
+            yield c0, indices[c0:c0 + chunk], c0 + chunk >= len(indices)
+
+    @staticmethod
+    def _collect(gen, dump_all_xstart):
+        """What a non-progressive entry returns of its loop `gen`: the last step's sample, or every step's x0-hat as a list."""
+        dump, final = [], None
+        for out in gen:
+            if dump_all_xstart:
+                dump.append(out["pred_xstart"])
+            final = out
+        return dump if dump_all_xstart else final["sample"]
+
     def _engine_loop(self, sampler, denoiser, cfg, img, indices, clip_denoised, model_kwargs, const_noise, eta, progress,
                      chunked, want_xstart=True, cond_fn=None):
         """Loop inside the library.  chunked=True (the non-progressive entry points): `noise_chunk`
@@ -599,22 +637,11 @@ class GaussianDiffusion:
         from .guidance import TargetGuide
         guide = self._target_guide_args(cond_fn, x) if isinstance(cond_fn, TargetGuide) else None
         per_step = cond_fn is not None and guide is None
-        if not chunked or per_step:
-            chunk = 1
-        elif in_kernel:
-            # no noise buffer; with an x0-hat dump the dump itself is bounded the same way
-            chunk = len(indices) if not want_xstart else max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
-        else:
-            chunk = max(1, min(int(self.noise_chunk), int(self.noise_chunk_bytes // (x.numel() * 4))))
+        chunk = 1 if not chunked or per_step else self._chunk_size(x, len(indices), not in_kernel, want_xstart)
         seed = int(th.randint(0, 2 ** 31 - 1, (1,)).item()) if philox and not reverse else 0
         if cfg is not None:
             eng.check_guidance_scale(scale)                 # once per loop (engine.CFG_SCALE_MAX), not per chunk or step
-        it = range(0, len(indices), chunk)
-        if progress:
-            from tqdm.auto import tqdm
-            it = tqdm(it)
-        for c0 in it:
-            idx = indices[c0:c0 + chunk]
+        for c0, idx, _ in self._chunks(indices, chunk, progress):
             noise = None
             if not philox:
                 noise = th.stack([self._draw(x, const_noise) for _ in idx])
@@ -761,15 +788,10 @@ class GaussianDiffusion:
                          dump_all_xstart=False, stop_timesteps=None):
         if const_noise:
             raise NotImplementedError()
-        dump, final = [], None
-        for out in self._sample_loop_progressive(
-                True, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, skip_timesteps,
-                init_image, randomize_class, cond_fn_with_grad, False, pred_xstart_in_graph, stop_timesteps, eta, chunked=True,
-                want_xstart=bool(dump_all_xstart)):
-            if dump_all_xstart:
-                dump.append(out["pred_xstart"])
-            final = out
-        return dump if dump_all_xstart else final["sample"]
+        return self._collect(self._sample_loop_progressive(
+            True, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress, skip_timesteps,
+            init_image, randomize_class, cond_fn_with_grad, False, pred_xstart_in_graph, stop_timesteps, eta, chunked=True,
+            want_xstart=bool(dump_all_xstart)), dump_all_xstart)
 
     # -- Clips of any length (no reference counterpart; diffusion/windows.py): overlapping windows of the model's own
     #    length, all windows of all clips as one batch, their shared frames stitched behind every step.
@@ -792,27 +814,8 @@ class GaussianDiffusion:
             raise ValueError(f"{who}: eta {eta} must be 0 (a stochastic step would need per-window noise unfolded from one long draw)")
         if cond_fn is not None:
             raise ValueError(f"{who}: cond_fn is not supported (guided windowed loops are not built)")
-        w = self._windows_setup(who, model, shape, plan, window, overlap, lengths, noise, model_kwargs, skip_timesteps, init_image,
-                                denoised_fn, device)
-        x, plan, indices = w.x, w.plan, w.indices
-        # one native call, or with the x0-hat dump chunks bounded like the other loops' ([steps, N, F, 1, W] at once otherwise)
-        chunk = len(indices) if not dump_all_xstart else max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
-        it = range(0, len(indices), chunk)
-        if progress:
-            from tqdm.auto import tqdm
-            it = tqdm(it)
-        dumps = []
-        for c0 in it:
-            idx = indices[c0:c0 + chunk]
-            last = c0 + chunk >= len(indices)
-            res = w.eng.sample_loop_windows(w.sch, x, plan, idx[0], idx[-1], cfg=w.cfg is not None, scale=w.scale,
-                                            mask=w.mask if w.mask is not None else w.nmask, motion=w.motion, mask_noise=w.nmask is not None,
-                                            clip_denoised=clip_denoised, dump_xstart=bool(dump_all_xstart),
-                                            fold_out=w.out_long if last else None)
-            if dump_all_xstart:
-                self._fold_dumps(res[1], len(idx), w, dumps)
-        result = dumps if dump_all_xstart else w.out_long
-        return (result, x) if return_windows else result
+        return self._windows_loop(who, model, shape, _eng.SAMPLER_DDIM, 0.0, None, plan, window, overlap, lengths, noise, clip_denoised,
+                                  model_kwargs, skip_timesteps, init_image, progress, dump_all_xstart, return_windows, denoised_fn, device)
 
     def _windows_setup(self, who, model, shape, plan, window, overlap, lengths, noise, model_kwargs, skip_timesteps, init_image,
                        denoised_fn, device):
@@ -911,18 +914,27 @@ class GaussianDiffusion:
         the unguided x0-hat.
         Refused: what ddim_sample_loop_windows refuses of model, plan and denoised_fn, an unknown sampler (ValueError), const_noise
         (NotImplementedError)."""
-        from . import windows as _win
-        from .guidance import TargetGuide
         who = "sample_loop_windows"
         if sampler not in ("ddim", "ddpm"):
             raise ValueError(f"{who}: unknown sampler {sampler!r} ('ddim' or 'ddpm': PLMS and the reverse DDIM step over windows are not built)")
         if const_noise:
             raise NotImplementedError(f"{who}: const_noise is not built for windows")
+        return self._windows_loop(who, model, shape, _eng.SAMPLER_DDPM if sampler == "ddpm" else _eng.SAMPLER_DDIM, eta, cond_fn, plan, window,
+                                  overlap, lengths, noise, clip_denoised, model_kwargs, skip_timesteps, init_image, progress, dump_all_xstart,
+                                  return_windows, denoised_fn, device)
+
+    def _windows_loop(self, who, model, shape, smp, eta, cond_fn, plan, window, overlap, lengths, noise, clip_denoised, model_kwargs,
+                      skip_timesteps, init_image, progress, dump_all_xstart, return_windows, denoised_fn, device):
+        """The body of both windowed entries (their arguments; `smp` an engine.SAMPLER_*; refusals raised by `who`).  The deterministic
+        subset -- SAMPLER_DDIM at eta 0 without a cond_fn -- draws nothing from torch's generator and goes through the library's
+        deterministic entry (DenoiserEngine.sample_loop_windows), everything else through window_sample_loop: the same loop behind
+        both, the first refusing what it cannot keep identical on shared frames."""
+        from . import windows as _win
+        from .guidance import TargetGuide
         w = self._windows_setup(who, model, shape, plan, window, overlap, lengths, noise, model_kwargs, skip_timesteps, init_image,
                                 denoised_fn, device)
         x, plan, indices = w.x, w.plan, w.indices
-        smp = _eng.SAMPLER_DDPM if sampler == "ddpm" else _eng.SAMPLER_DDIM
-        noisy = sampler == "ddpm" or eta != 0.0                 # the step has a noise term: the loop reads a buffer
+        noisy = smp == _eng.SAMPLER_DDPM or eta != 0.0          # the step has a noise term: the loop reads a buffer
         philox = self.noise_source == "philox"
         guide = None
         if isinstance(cond_fn, TargetGuide):
@@ -934,24 +946,12 @@ class GaussianDiffusion:
                 long_op(cond_fn.target, "target"), None if cond_fn.mask is None else long_op(cond_fn.mask, "guide mask"),
                 wt if wt.numel() == 1 else wt[plan.win_clip_tensor().to(wt.device)], cond_fn.alphas_cumprod), x)
         per_step = cond_fn is not None and guide is None
-        bound = max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
-        if per_step:
-            chunk = 1
-        elif noisy:
-            chunk = max(1, min(int(self.noise_chunk), bound))
-        else:
-            chunk = len(indices) if not dump_all_xstart else bound
+        chunk = 1 if per_step else self._chunk_size(x, len(indices), noisy, dump_all_xstart)
         seed = int(th.randint(0, 2 ** 31 - 1, (1,)).item()) if philox and noisy else 0
         if w.cfg is not None:
-            w.eng.check_guidance_scale(w.scale)
-        it = range(0, len(indices), chunk)
-        if progress:
-            from tqdm.auto import tqdm
-            it = tqdm(it)
+            w.eng.check_guidance_scale(w.scale, stacklevel=4)       # (the warning names the caller of the public entry)
         dumps = []
-        for c0 in it:
-            idx = indices[c0:c0 + chunk]
-            last = c0 + chunk >= len(indices)
+        for c0, idx, last in self._chunks(indices, chunk, progress):
             buf = None
             if noisy and philox:
                 buf = _win.noise_windows(plan, w.shape[1], seed + c0, 0, len(idx))
@@ -962,10 +962,13 @@ class GaussianDiffusion:
                 t = th.full((plan.n_clips,), int(idx[0]), device=x.device, dtype=th.long)
                 grad = self._cond_gradient(cond_fn, w.out_long, t, model_kwargs)
                 guide = _eng.guide_args(x, grad=_win.unfold(grad.to(device=x.device).contiguous(), plan))
-            res = w.eng.window_sample_loop(w.sch, x, plan, idx[0], idx[-1], smp, eta, cfg=w.cfg is not None, scale=w.scale,
-                                           mask=w.mask if w.mask is not None else w.nmask, motion=w.motion,
-                                           mask_noise=w.nmask is not None, clip_denoised=clip_denoised, noise=buf, guide=guide,
-                                           dump_xstart=bool(dump_all_xstart), fold_out=w.out_long if last else None)
+            kw = dict(cfg=w.cfg is not None, scale=w.scale, mask=w.mask if w.mask is not None else w.nmask, motion=w.motion,
+                      mask_noise=w.nmask is not None, clip_denoised=clip_denoised, dump_xstart=bool(dump_all_xstart),
+                      fold_out=w.out_long if last else None)
+            if noisy or cond_fn is not None:
+                res = w.eng.window_sample_loop(w.sch, x, plan, idx[0], idx[-1], smp, eta, noise=buf, guide=guide, **kw)
+            else:
+                res = w.eng.sample_loop_windows(w.sch, x, plan, idx[0], idx[-1], **kw)
             if dump_all_xstart:
                 self._fold_dumps(res[1], len(idx), w, dumps)
         result = dumps if dump_all_xstart else w.out_long
@@ -994,13 +997,8 @@ class GaussianDiffusion:
     def ddim_reverse_sample_loop(self, model, x_start, num_steps=None, clip_denoised=True, model_kwargs=None, device=None,
                                  progress=False, dump_all_xstart=False):
         """DDIM inversion: x at index num_steps of the deterministic process that starts at `x_start` (or every step's x0-hat)."""
-        dump, final = [], None
-        for out in self._reverse_loop(model, x_start, num_steps, clip_denoised, model_kwargs, device, progress, True,
-                                      bool(dump_all_xstart)):
-            if dump_all_xstart:
-                dump.append(out["pred_xstart"])
-            final = out
-        return dump if dump_all_xstart else final["sample"]
+        return self._collect(self._reverse_loop(model, x_start, num_steps, clip_denoised, model_kwargs, device, progress, True,
+                                                bool(dump_all_xstart)), dump_all_xstart)
 
     def ddim_sample_loop_from(self, model, x_t, num_steps, eta=0.0, clip_denoised=True, denoised_fn=None, cond_fn=None,
                               model_kwargs=None, device=None, progress=False, dump_all_xstart=False):
@@ -1010,13 +1008,9 @@ class GaussianDiffusion:
         if not 1 <= n <= self.num_timesteps:
             raise ValueError(f"ddim_sample_loop_from: num_steps {n} outside 1..{self.num_timesteps}")
         device = self._loop_device(model, device)
-        dump, final = [], None
-        for out in self._steps_from(_eng.SAMPLER_DDIM, model, device, x_t.to(device), list(range(n))[::-1], clip_denoised, denoised_fn,
-                                    cond_fn, model_kwargs, False, eta, progress, True, bool(dump_all_xstart)):
-            if dump_all_xstart:
-                dump.append(out["pred_xstart"])
-            final = out
-        return dump if dump_all_xstart else final["sample"]
+        return self._collect(self._steps_from(_eng.SAMPLER_DDIM, model, device, x_t.to(device), list(range(n))[::-1], clip_denoised,
+                                              denoised_fn, cond_fn, model_kwargs, False, eta, progress, True, bool(dump_all_xstart)),
+                             dump_all_xstart)
 
     # -- PLMS (reference :1084-1279): Pseudo Linear Multistep, orders 1..4.  No noise term: nothing is drawn anywhere below.
     def plms_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
@@ -1027,11 +1021,7 @@ class GaussianDiffusion:
         or, for the step that opens a chain (`old_out=None`, order > 1: the two-evaluation Pseudo Improved Euler step), a new list.
         Departure from the reference: that opening step at index 0 raises ValueError (the reference evaluates the model at
         t - 1 = -1 there, which wraps to the last table entry)."""
-        if not int(order) or not 1 <= order <= 4:
-            raise ValueError('order is invalid (should be int from 1-4).')
-        if cond_fn is not None or denoised_fn is not None:
-            raise NotImplementedError("plms_sample: cond_fn / denoised_fn are not built for the PLMS sampler (guided PLMS is out of scope); "
-                                      "p_sample, ddim_sample and their loops take them")
+        _plms_refuse(order, cond_fn, denoised_fn)
         sch = self._schedule(x.device)
         mask, motion = self._inpaint_pair(model_kwargs)
         mean_type = {ModelMeanType.START_X: 0, ModelMeanType.EPSILON: 1, ModelMeanType.PREVIOUS_X: 2}[self.model_mean_type]
@@ -1069,18 +1059,10 @@ class GaussianDiffusion:
         sch = self._schedule(img.device)
         x = img.contiguous().float().clone()
         hist = th.empty((3,) + tuple(x.shape), dtype=th.float32, device=x.device) if order > 1 else None
-        if not chunked:
-            chunk = 1
-        else:
-            chunk = len(indices) if not want_xstart else max(1, int(self.noise_chunk_bytes // (x.numel() * 4)))
+        chunk = self._chunk_size(x, len(indices), False, want_xstart) if chunked else 1
         if cfg is not None:
             eng.check_guidance_scale(scale)
-        it = range(0, len(indices), chunk)
-        if progress:
-            from tqdm.auto import tqdm
-            it = tqdm(it)
-        for c0 in it:
-            idx = indices[c0:c0 + chunk]
+        for c0, idx, _ in self._chunks(indices, chunk, progress):
             res = eng.sample_loop_plms(sch, x, idx[0], idx[-1], order=order, steps_done=c0, hist=hist, cfg=cfg is not None, scale=scale,
                                        mask=mask, motion=motion, clip_denoised=clip_denoised, dump_xstart=want_xstart)
             dump = res[1] if want_xstart else None
@@ -1096,11 +1078,7 @@ class GaussianDiffusion:
                          progress, chunked, want_xstart):
         """The steps of every PLMS loop entry from `img` as it is through the descending `indices`: inside the library under the
         condition `_steps_from` uses, step by step through `plms_sample` otherwise."""
-        if not int(order) or not 1 <= order <= 4:
-            raise ValueError('order is invalid (should be int from 1-4).')
-        if cond_fn is not None or denoised_fn is not None:
-            raise NotImplementedError("plms_sample: cond_fn / denoised_fn are not built for the PLMS sampler (guided PLMS is out of scope); "
-                                      "p_sample, ddim_sample and their loops take them")
+        _plms_refuse(order, cond_fn, denoised_fn)
         if order > 1 and indices[0] == 0:
             raise ValueError("plms_sample_loop: a chain of order > 1 cannot start at index 0 (its first step evaluates the model at t - 1)")
         denoiser, cfg, _ = _unwrap(model)
@@ -1137,11 +1115,7 @@ class GaussianDiffusion:
                    init_image, randomize_class, cond_fn_with_grad, order, chunked, want_xstart):
         if randomize_class:
             raise NotImplementedError("randomize_class is an image-diffusion leftover, unused by this model family")
-        if not int(order) or not 1 <= order <= 4:
-            raise ValueError('order is invalid (should be int from 1-4).')
-        if cond_fn is not None or denoised_fn is not None:
-            raise NotImplementedError("plms_sample: cond_fn / denoised_fn are not built for the PLMS sampler (guided PLMS is out of scope); "
-                                      "p_sample, ddim_sample and their loops take them")
+        _plms_refuse(order, cond_fn, denoised_fn)
         if order > 1 and self.num_timesteps - skip_timesteps - 1 == 0:
             raise ValueError("plms_sample_loop: a chain of order > 1 cannot start at index 0 (its first step evaluates the model at t - 1)")
         device, img, indices = self._loop_setup(model, shape, noise, device, skip_timesteps, init_image, None, model_kwargs)
@@ -1152,11 +1126,8 @@ class GaussianDiffusion:
                          device=None, progress=False, skip_timesteps=0, init_image=None, randomize_class=False,
                          cond_fn_with_grad=False, order=2):
         """The final sample of plms_sample_loop_progressive (reference :1168-1208; the same three departures)."""
-        final = None
-        for out in self._plms_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
-                                   skip_timesteps, init_image, randomize_class, cond_fn_with_grad, order, True, False):
-            final = out
-        return final["sample"]
+        return self._collect(self._plms_loop(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, progress,
+                                             skip_timesteps, init_image, randomize_class, cond_fn_with_grad, order, True, False), False)
 
     def plms_sample_loop_from(self, model, x_t, num_steps, order=2, clip_denoised=True, denoised_fn=None, cond_fn=None,
                               model_kwargs=None, device=None, progress=False, dump_all_xstart=False):
@@ -1166,13 +1137,8 @@ class GaussianDiffusion:
         if not 1 <= n <= self.num_timesteps:
             raise ValueError(f"plms_sample_loop_from: num_steps {n} outside 1..{self.num_timesteps}")
         device = self._loop_device(model, device)
-        dump, final = [], None
-        for out in self._plms_steps_from(model, device, x_t.to(device), list(range(n))[::-1], clip_denoised, denoised_fn, cond_fn,
-                                         model_kwargs, False, order, progress, True, bool(dump_all_xstart)):
-            if dump_all_xstart:
-                dump.append(out["pred_xstart"])
-            final = out
-        return dump if dump_all_xstart else final["sample"]
+        return self._collect(self._plms_steps_from(model, device, x_t.to(device), list(range(n))[::-1], clip_denoised, denoised_fn, cond_fn,
+                                                   model_kwargs, False, order, progress, True, bool(dump_all_xstart)), dump_all_xstart)
 
     # ------------------------------------------------------------------------------ variational bound
     def _vb_true_logvar(self, device):

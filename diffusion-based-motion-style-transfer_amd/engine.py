@@ -694,18 +694,15 @@ class DenoiserEngine:
         return out
 
     # ------------------------------------------------------------------------------ sampling
-    def sample_loop(self, schedule, x, t_start, t_end=0, sampler=SAMPLER_DDPM, eta=0.0, cfg=False, scale=None,
-                    mask=None, motion=None, mask_noise=True, clip_denoised=False, noise=None, seed=None,
-                    dump_xstart=False, guide=None):
-        """Run diffusion indices t_start..t_end in place on `x` ([B,F,1,T] float32 GPU tensor): downward (t_start >= t_end) for
-        SAMPLER_DDPM / SAMPLER_DDIM, upward (t_start <= t_end; x leaves as x at index t_end + 1) for SAMPLER_DDIM_REVERSE.
-        noise: [nsteps,B,F,1,T] tensor (injected draws) or None -> in-kernel Philox with `seed`; the reverse sampler reads neither.
-        guide: a `guide_args(...)` pair -> mst_sample_loop_guided (p_sample_loop / ddim_sample_loop with a cond_fn); the x0-hat dump is
-        then the UNGUIDED x0-hat of every step.
-        Returns x (and the [nsteps,B,F,1,T] x0-hat dump, entry j = executed step j, when requested)."""
+    def _loop_request(self, x, t_start, t_end, sampler, eta, cfg, scale, mask, motion, mask_noise, clip_denoised, dump_xstart,
+                      noise=None, seed=None):
+        """What every sampling entry hands the library for a loop over t_start..t_end in place on `x`: the filled MstLoopArgs, the
+        list of tensors its pointers read (the caller keeps it alive in `_loop_keepalive`) and the [nsteps,B,F,1,T] x0-hat dump (None
+        unless `dump_xstart`).  noise: one draw of x's shape per step ([nsteps,B,F,1,T], or x's own shape for a single step), or
+        None -> MST_NOISE_PHILOX with `seed`."""
         assert _need_gpu(x, "x").dtype == torch.float32 and x.is_contiguous()
         if cfg:
-            self.check_guidance_scale(scale)
+            self.check_guidance_scale(scale, stacklevel=4)    # (the warning names the caller of the public method)
         B, F, one, T = x.shape
         nsteps = abs(t_start - t_end) + 1                  # (a range against the sampler's direction is refused by the library)
         a = N.MstLoopArgs()
@@ -715,7 +712,6 @@ class DenoiserEngine:
         keep = []
         if noise is not None:
             assert noise.numel() == nsteps * x.numel(), (noise.shape, nsteps, x.shape)
-            # every step's draw has x's shape: [nsteps, B, F, 1, T], or x's own shape for a single step
             single = nsteps == 1 and isinstance(noise, torch.Tensor) and noise.dim() == x.dim()
             noise = _operand(noise, tuple(x.shape) if single else (nsteps,) + tuple(x.shape), "noise", RULE_EQUAL, self.device)
             a.noise_mode, a.noise_dev = NOISE_BUFFER, noise.data_ptr()
@@ -733,6 +729,31 @@ class DenoiserEngine:
         if dump_xstart:
             dump = torch.empty((nsteps,) + tuple(x.shape), dtype=torch.float32, device=self.device)
             a.xstart_dump_dev = dump.data_ptr()
+        return a, keep, dump
+
+    def _windowed_call(self, x, plan, fold_out, call):
+        """`call()` (a windowed library entry on the windows `x` of `plan`) with the plan's fold set to `fold_out` for its duration."""
+        if fold_out is not None:
+            want = (plan.n_clips, x.shape[1], x.shape[2], plan.long_frames)
+            assert fold_out.is_cuda and fold_out.dtype == torch.float32 and fold_out.is_contiguous() and tuple(fold_out.shape) == want, \
+                f"fold_out: a contiguous float32 {want} tensor"
+        N.check(N.lib().mst_window_plan_set_fold(plan.handle, N.ptr(fold_out)))
+        try:
+            N.check(call())
+        finally:
+            N.check(N.lib().mst_window_plan_set_fold(plan.handle, None))
+
+    def sample_loop(self, schedule, x, t_start, t_end=0, sampler=SAMPLER_DDPM, eta=0.0, cfg=False, scale=None,
+                    mask=None, motion=None, mask_noise=True, clip_denoised=False, noise=None, seed=None,
+                    dump_xstart=False, guide=None):
+        """Run diffusion indices t_start..t_end in place on `x` ([B,F,1,T] float32 GPU tensor): downward (t_start >= t_end) for
+        SAMPLER_DDPM / SAMPLER_DDIM, upward (t_start <= t_end; x leaves as x at index t_end + 1) for SAMPLER_DDIM_REVERSE.
+        noise: [nsteps,B,F,1,T] tensor (injected draws) or None -> in-kernel Philox with `seed`; the reverse sampler reads neither.
+        guide: a `guide_args(...)` pair -> mst_sample_loop_guided (p_sample_loop / ddim_sample_loop with a cond_fn); the x0-hat dump is
+        then the UNGUIDED x0-hat of every step.
+        Returns x (and the [nsteps,B,F,1,T] x0-hat dump, entry j = executed step j, when requested)."""
+        a, keep, dump = self._loop_request(x, t_start, t_end, sampler, eta, cfg, scale, mask, motion, mask_noise, clip_denoised, dump_xstart,
+                                           noise, seed)
         if guide is not None:
             N.check(N.lib().mst_sample_loop_guided(self.handle, schedule.handle, C.byref(a), C.byref(guide[0]), N.stream_ptr(self.device)))
             keep.append(guide[1])
@@ -747,37 +768,11 @@ class DenoiserEngine:
         every step (mst_sample_loop_windows): equal, bit for bit, to one-step `sample_loop` calls with `windows.stitch_` between them.
         fold_out: a [C,F,1,L] float32 tensor the last stitch also writes the long clips into (None: no fold).  Nothing is drawn.
         Returns x (and the [nsteps,N,F,1,W] x0-hat dump of the windows, as the steps wrote it, when requested)."""
-        assert _need_gpu(x, "x").dtype == torch.float32 and x.is_contiguous()
-        if cfg:
-            self.check_guidance_scale(scale)
-        B, F, one, T = x.shape
-        nsteps = abs(t_start - t_end) + 1
-        a = N.MstLoopArgs()
-        a.batch, a.frames, a.cfg, a.sampler = B, T, int(bool(cfg)), SAMPLER_DDIM
-        a.mask_noise, a.clip_denoised = int(bool(mask_noise)), int(bool(clip_denoised))
-        a.t_start, a.t_end, a.eta = int(t_start), int(t_end), 0.0
-        a.noise_mode, a.seed = NOISE_PHILOX, 0              # sigma is 0 at eta 0: the draw is multiplied away
-        keep = []
-        mask, motion = _mask_pair(mask, motion, x.shape, self.device)
-        scale = None if scale is None else _operand(scale, (B,), "scale", RULE_SCALE, self.device)
-        for name, val in (("scale_dev", scale), ("inpainting_mask_dev", mask), ("inpainted_motion_dev", motion)):
-            if val is not None:
-                keep.append(val)
-                setattr(a, name, val.data_ptr())
-        a.x_dev = x.data_ptr()
-        dump = None
-        if dump_xstart:
-            dump = torch.empty((nsteps,) + tuple(x.shape), dtype=torch.float32, device=self.device)
-            a.xstart_dump_dev = dump.data_ptr()
-        if fold_out is not None:
-            want = (plan.n_clips, F, one, plan.long_frames)
-            assert fold_out.is_cuda and fold_out.dtype == torch.float32 and fold_out.is_contiguous() and tuple(fold_out.shape) == want, \
-                f"fold_out: a contiguous float32 {want} tensor"
-        N.check(N.lib().mst_window_plan_set_fold(plan.handle, N.ptr(fold_out)))
-        try:
-            N.check(N.lib().mst_sample_loop_windows(self.handle, schedule.handle, C.byref(a), plan.handle, N.stream_ptr(self.device)))
-        finally:
-            N.check(N.lib().mst_window_plan_set_fold(plan.handle, None))
+        # (MST_NOISE_PHILOX, seed 0: sigma is 0 at eta 0, the draw is multiplied away)
+        a, keep, dump = self._loop_request(x, t_start, t_end, SAMPLER_DDIM, 0.0, cfg, scale, mask, motion, mask_noise, clip_denoised,
+                                           dump_xstart, seed=0)
+        self._windowed_call(x, plan, fold_out, lambda: N.lib().mst_sample_loop_windows(
+            self.handle, schedule.handle, C.byref(a), plan.handle, N.stream_ptr(self.device)))
         self._loop_keepalive = keep
         return (x, dump) if dump_xstart else x
 
@@ -790,47 +785,14 @@ class DenoiserEngine:
         guide: a `guide_args(...)` pair on the windows' operands.  fold_out: a [C,F,1,L] float32 tensor the last stitch also writes the
         long clips into (None: no fold).  Returns x (and the [nsteps,N,F,1,W] x0-hat dump of the windows -- with a guide the unguided
         x0-hat -- as the steps wrote it, when requested)."""
-        assert _need_gpu(x, "x").dtype == torch.float32 and x.is_contiguous()
-        if cfg:
-            self.check_guidance_scale(scale)
-        B, F, one, T = x.shape
-        nsteps = abs(t_start - t_end) + 1
-        a = N.MstLoopArgs()
-        a.batch, a.frames, a.cfg, a.sampler = B, T, int(bool(cfg)), int(sampler)
-        a.mask_noise, a.clip_denoised = int(bool(mask_noise)), int(bool(clip_denoised))
-        a.t_start, a.t_end, a.eta = int(t_start), int(t_end), float(eta)
-        keep = []
-        if noise is not None:
-            assert noise.numel() == nsteps * x.numel(), (noise.shape, nsteps, x.shape)
-            single = nsteps == 1 and isinstance(noise, torch.Tensor) and noise.dim() == x.dim()
-            noise = _operand(noise, tuple(x.shape) if single else (nsteps,) + tuple(x.shape), "noise", RULE_EQUAL, self.device)
-            a.noise_mode, a.noise_dev = NOISE_BUFFER, noise.data_ptr()
-            keep.append(noise)
-        else:
-            a.noise_mode, a.seed = NOISE_PHILOX, 0              # taken only where sigma is 0 (DDIM at eta 0): the draw is multiplied away
-        mask, motion = _mask_pair(mask, motion, x.shape, self.device)
-        scale = None if scale is None else _operand(scale, (B,), "scale", RULE_SCALE, self.device)
-        for name, val in (("scale_dev", scale), ("inpainting_mask_dev", mask), ("inpainted_motion_dev", motion)):
-            if val is not None:
-                keep.append(val)
-                setattr(a, name, val.data_ptr())
-        a.x_dev = x.data_ptr()
-        dump = None
-        if dump_xstart:
-            dump = torch.empty((nsteps,) + tuple(x.shape), dtype=torch.float32, device=self.device)
-            a.xstart_dump_dev = dump.data_ptr()
-        if fold_out is not None:
-            want = (plan.n_clips, F, one, plan.long_frames)
-            assert fold_out.is_cuda and fold_out.dtype == torch.float32 and fold_out.is_contiguous() and tuple(fold_out.shape) == want, \
-                f"fold_out: a contiguous float32 {want} tensor"
+        # (without a buffer MST_NOISE_PHILOX, seed 0: taken only where sigma is 0 -- DDIM at eta 0 -- and the draw is multiplied away)
+        a, keep, dump = self._loop_request(x, t_start, t_end, sampler, eta, cfg, scale, mask, motion, mask_noise, clip_denoised, dump_xstart,
+                                           noise, seed=0)
         if guide is not None:
             keep.append(guide[1])
-        N.check(N.lib().mst_window_plan_set_fold(plan.handle, N.ptr(fold_out)))
-        try:
-            N.check(N.lib().mst_window_sample_loop(self.handle, schedule.handle, C.byref(a), plan.handle,
-                                                   C.byref(guide[0]) if guide is not None else None, N.stream_ptr(self.device)))
-        finally:
-            N.check(N.lib().mst_window_plan_set_fold(plan.handle, None))
+        self._windowed_call(x, plan, fold_out, lambda: N.lib().mst_window_sample_loop(
+            self.handle, schedule.handle, C.byref(a), plan.handle, C.byref(guide[0]) if guide is not None else None,
+            N.stream_ptr(self.device)))
         self._loop_keepalive = keep
         return (x, dump) if dump_xstart else x
 
@@ -841,37 +803,18 @@ class DenoiserEngine:
         chain: for order > 1 its first step is the two-evaluation Euler step).  A k-step call equals k one-step calls with steps_done
         carried forward, bit for bit.  Returns x (and the x0-hat dump, first evaluation of every step, when requested).
         noise, seed, eta, mask_noise: handed to the library as given and ignored there (the step has no noise term)."""
-        assert _need_gpu(x, "x").dtype == torch.float32 and x.is_contiguous()
-        if cfg:
-            self.check_guidance_scale(scale)
-        B, F, one, T = x.shape
-        nsteps = abs(t_start - t_end) + 1
-        a = N.MstLoopArgs()
-        a.batch, a.frames, a.cfg, a.sampler = B, T, int(bool(cfg)), SAMPLER_PLMS
-        a.clip_denoised = int(bool(clip_denoised))
-        a.t_start, a.t_end, a.eta, a.mask_noise = int(t_start), int(t_end), float(eta), int(bool(mask_noise))
-        a.noise_mode, a.seed = NOISE_PHILOX, int(seed or 0)
-        if noise is not None:
+        a, keep, dump = self._loop_request(x, t_start, t_end, SAMPLER_PLMS, eta, cfg, scale, mask, motion, mask_noise, clip_denoised,
+                                           dump_xstart, seed=seed)
+        if noise is not None:                              # as given: no shape is asked of a buffer that is never read
             a.noise_mode, a.noise_dev = NOISE_BUFFER, noise.data_ptr()
+            keep.append(noise)
         pl = N.MstPlmsArgs()
         pl.order, pl.steps_done = int(order), int(steps_done)
-        keep = [noise]
         if hist is not None:
             assert hist.is_cuda and hist.dtype == torch.float32 and hist.is_contiguous() and hist.numel() == 3 * x.numel(), \
                 "hist: a contiguous float32 [3,B,F,1,T] ring"
             pl.hist_dev = hist.data_ptr()
             keep.append(hist)
-        mask, motion = _mask_pair(mask, motion, x.shape, self.device)
-        scale = None if scale is None else _operand(scale, (B,), "scale", RULE_SCALE, self.device)
-        for name, val in (("scale_dev", scale), ("inpainting_mask_dev", mask), ("inpainted_motion_dev", motion)):
-            if val is not None:
-                keep.append(val)
-                setattr(a, name, val.data_ptr())
-        a.x_dev = x.data_ptr()
-        dump = None
-        if dump_xstart:
-            dump = torch.empty((nsteps,) + tuple(x.shape), dtype=torch.float32, device=self.device)
-            a.xstart_dump_dev = dump.data_ptr()
         N.check(N.lib().mst_sample_loop_plms(self.handle, schedule.handle, C.byref(a), C.byref(pl), N.stream_ptr(self.device)))
         self._loop_keepalive = keep
         return (x, dump) if dump_xstart else x
@@ -915,9 +858,9 @@ class DenoiserEngine:
             rc = 0
         N.check(rc)
 
-    def check_guidance_scale(self, scale):
-        """Warn (once per engine, through `warnings.warn`) when a guided call's scale puts the default path above the 1e-3 bar,
-        i.e. above CFG_SCALE_MAX.  A device tensor costs one host synchronisation the first time that tensor object (at that
+    def check_guidance_scale(self, scale, stacklevel=3):
+        """Warn (once per engine, through `warnings.warn`, whose `stacklevel` this is: 3 names the caller of a method that calls this
+        directly) when a guided call's scale puts the default path above the 1e-3 bar, i.e. above CFG_SCALE_MAX.  A device tensor costs one host synchronisation the first time that tensor object (at that
         version) is seen, none after: loops call this once, not per step."""
         if scale is None or self._precise_on or getattr(self, "_cfg_warned", False):
             return
@@ -936,7 +879,7 @@ class DenoiserEngine:
             import warnings
             warnings.warn(f"mst_amd: classifier-free guidance scale {g:g} is above CFG_SCALE_MAX = {CFG_SCALE_MAX:g}: the f16 MFMA "
                           "operands' rounding grows with the scale and may exceed 1e-3 relative L2; DenoiserEngine.set_precise(True) / "
-                          "MST_PRECISE=1 splits every operand (hi + lo)", stacklevel=3)
+                          "MST_PRECISE=1 splits every operand (hi + lo)", stacklevel=stacklevel)
 
     def set_trunk_groups(self, on=True):
         """The encoder stack of a sampling step as ONE launch of resident workgroup groups (csrc/mst_trunk.h); bit-identical results."""

@@ -261,7 +261,8 @@ int mst_sample_loop_guided(mst_engine* e, const mst_schedule* s, const mst_loop_
  *                       Refused, each by name: any sampler but MST_SAMPLER_DDIM; eta != 0 (for the deterministic step x_{t-1} is linear
  *                       in x_t and x0-hat, so windows that start from one long x_T hold identical values on shared frames after every
  *                       stitch, and the mean is a mean over x0-hat alone); batch != the plan's windows; frames != the plan's window; a
- *                       plan on another device.  It takes no guide: mst_window_sample_loop does.
+ *                       plan on another device.  It takes no guide: mst_window_sample_loop does.  It is no implementation of its own:
+ *                       the deterministic subset of mst_window_sample_loop, over the same code, with its two refusals in front.
  *   mst_window_noise    extends mst_philox_normal to windows: out_dev [nsteps,N,F,1,W], the layout an MST_NOISE_BUFFER loop reads (step
  *                       j at j * N*F*W).  Entry j = unfold(Z_j), Z_j [C,F,1,L] = mst_philox_normal(C, F, L, seed, step0 + j): element
  *                       (c, f, l) is component l & 3 of the four normals of counter (l >> 2, f, c, step0 + j) under `seed` -- the noise

@@ -4,16 +4,13 @@ The kernels behind Schedule.q_sample / step / step_guided, DenoiserEngine.forwar
 base + i over B * per_clip elements (B for `scale`): whatever reaches the library must be a float32 contiguous tensor of exactly that
 many elements.  Part one holds the helper's three rules; part two drives the entry points with the library replaced by a recording
 stub (and the device check, which is separate from the shape logic, switched off) and checks every pointer handed over."""
-import ctypes as C
-import types
-
 import numpy as np
 import pytest
 import torch
 
 import mst_amd  # noqa: F401
-from mst_amd import _native as N
 from mst_amd import engine as E
+from lib_stub import install, stub_engine, stub_schedule
 
 B, F, T = 3, 5, 7
 SHAPE = (B, F, 1, T)
@@ -113,48 +110,16 @@ def test_pair_and_noise_mask_roles():
 
 
 # ------------------------------------------------------------------------------------------ the entry points over a recording stub
-class _Lib:
-    """Every entry point returns 0 and records its arguments."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("mst_"):
-            raise AttributeError(name)
-
-        def fn(*args):
-            self.calls.append((name, args))
-            return 0
-        return fn
-
-
 @pytest.fixture
 def stub(monkeypatch):
-    lib, seen = _Lib(), []
-
-    def ptr(t):
-        if t is None:
-            return None
-        seen.append(t)
-        return C.c_void_p(t.data_ptr())
-    monkeypatch.setattr(N, "lib", lambda: lib)
-    monkeypatch.setattr(N, "ptr", ptr)
-    monkeypatch.setattr(N, "stream_ptr", lambda device: None)
-    monkeypatch.setattr(E, "_need_gpu", lambda t, what: t)
-    return types.SimpleNamespace(lib=lib, seen=seen)
+    return install(monkeypatch)
 
 
-def _schedule():
-    s = E.Schedule.__new__(E.Schedule)
-    s.handle, s.num_steps, s.device = None, 20, torch.device("cpu")
-    return s
+_schedule = stub_schedule
 
 
 def _engine():
-    e = E.DenoiserEngine.__new__(E.DenoiserEngine)
-    e.handle, e.device, e.feats, e._precise_on = None, torch.device("cpu"), F, False
-    return e
+    return stub_engine(F)
 
 
 def _all_full(tensors):
