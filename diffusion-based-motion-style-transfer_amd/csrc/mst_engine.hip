@@ -42,6 +42,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_clip.h"
 #include "mst_smpl.h"
 #include "mst_smplify.h"
+#include "mst_track.h"
 
 using namespace mst;
 
@@ -4007,6 +4008,76 @@ extern "C" int mst_smplify_objective(int32_t stage, int32_t nj, int32_t frames, 
         hipLaunchKernelGGL(k_smplify_sum, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)per_frame, frames, loss);
         HIPCHECK(hipGetLastError());
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ pose tracks (mst_track.h)
+// Neither kernel keeps anything on chip, so the bounds are sanity checks on the arguments and the same on every device.
+extern "C" int mst_track_max_frames(int32_t joints) {
+    if (joints < 1 || joints > kTrackMaxJoints) {
+        fail("mst_track_max_frames: joints %d outside 1..%d", joints, kTrackMaxJoints);
+        return -1;
+    }
+    return kTrackMaxFrames;
+}
+static int track_rate(const char* what, int32_t batch, int32_t frames, int32_t up, int32_t down) {
+    if (batch < 1) return fail("%s: batch %d < 1", what, batch);
+    if (frames < 2) return fail("%s: frames %d < 2: a track is resampled interval by interval", what, frames);
+    if (frames > kTrackMaxFrames) return fail("%s: frames %d > %d (mst_track_max_frames)", what, frames, kTrackMaxFrames);
+    if (up < 1 || up > kTrackMaxRate || down < 1 || down > kTrackMaxRate) return fail("%s: rate %d / %d: each outside 1..%d", what, up, down, kTrackMaxRate);
+    return 0;
+}
+static int track_out_frames(int32_t frames, int32_t up, int32_t down) { return (int)(((long long)(frames - 1) * up + down - 1) / down); }
+
+extern "C" int mst_track_resample(const float* quats, const float* points, const int32_t* lengths, int32_t batch, int32_t frames,
+                                  int32_t joints, int32_t num_points, int32_t up, int32_t down, int32_t shortest, float* quats_out,
+                                  float* points_out, void* stream) {
+    CHECK(track_rate("mst_track_resample", batch, frames, up, down));
+    if (joints < 0 || joints > kTrackMaxJoints) return fail("mst_track_resample: joints %d outside 0..%d", joints, kTrackMaxJoints);
+    if (num_points < 0 || num_points > kTrackMaxJoints) return fail("mst_track_resample: points %d outside 0..%d", num_points, kTrackMaxJoints);
+    if (joints + num_points < 1) return fail("mst_track_resample: neither a rotation track nor a point track");
+    if ((joints > 0) != (quats != nullptr) || (joints > 0) != (quats_out != nullptr))
+        return fail("mst_track_resample: %d joints but the rotation track or its output is %s", joints, joints ? "null" : "given");
+    if ((num_points > 0) != (points != nullptr) || (num_points > 0) != (points_out != nullptr))
+        return fail("mst_track_resample: %d points but the point track or its output is %s", num_points, num_points ? "null" : "given");
+    if ((quats && quats_out == quats) || (points && points_out == points)) return fail("mst_track_resample: an output may not be its input");
+    TrackResampleArgs p{};
+    p.quats = quats; p.points = points; p.lengths = lengths; p.B = batch; p.T = frames; p.J = joints; p.P = num_points;
+    p.Tout = track_out_frames(frames, up, down); p.up = up; p.down = down; p.shortest = shortest != 0;
+    p.quats_out = quats_out; p.points_out = points_out;
+    const long long n = (long long)batch * p.Tout * (joints + num_points), blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail("mst_track_resample: %lld outputs are more than one launch takes", n);
+    hipLaunchKernelGGL(k_track_resample, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_track_joints(const float* rotations, int32_t is_matrix, int32_t rot_joints, const float* transl, const float* betas,
+                                const float* est_joints, int32_t est_joint_count, const int32_t* lengths, int32_t batch, int32_t frames,
+                                int32_t up, int32_t down, int32_t shortest, int32_t with_trans, const float* j0, const float* jdirs,
+                                const int32_t* parents, float* out, float* est_out, void* stream) {
+    CHECK(track_rate("mst_track_joints", batch, frames, up, down));
+    if (batch > 65535) return fail("mst_track_joints: batch %d > 65535", batch);
+    if (rot_joints < kTrackChain || rot_joints > kTrackMaxJoints)
+        return fail("mst_track_joints: %d rotations a frame outside %d..%d (the chain reads the first %d)", rot_joints, kTrackChain, kTrackMaxJoints, kTrackChain);
+    if (!rotations || !betas || !j0 || !jdirs || !parents || !out) return fail("mst_track_joints: null rotations, betas, joint tables, parents or output");
+    if (with_trans && !transl) return fail("mst_track_joints: with_trans without a translation track");
+    if ((est_joints != nullptr) != (est_out != nullptr)) return fail("mst_track_joints: the estimator's joint track and its output come together");
+    if (est_joints && (est_joint_count < kTrackChain || est_joint_count > kTrackMaxJoints))
+        return fail("mst_track_joints: %d estimator joints a frame outside %d..%d", est_joint_count, kTrackChain, kTrackMaxJoints);
+    if (parents[0] != -1) return fail("mst_track_joints: parents[0] = %d, the root's is -1", parents[0]);
+    TrackJointsArgs p{};
+    p.parents[0] = -1;
+    for (int j = 1; j < kTrackChain; j++) {
+        if (parents[j] < 0 || parents[j] >= j) return fail("mst_track_joints: parents[%d] = %d is not an earlier joint", j, parents[j]);
+        p.parents[j] = (signed char)parents[j];
+    }
+    p.rot = rotations; p.rot_mat = is_matrix != 0; p.Jr = rot_joints; p.transl = transl; p.betas = betas; p.extra = est_joints;
+    p.Je = est_joints ? est_joint_count : 0; p.lengths = lengths; p.B = batch; p.T = frames; p.Tout = track_out_frames(frames, up, down);
+    p.up = up; p.down = down; p.shortest = shortest != 0; p.with_trans = with_trans != 0; p.J0 = j0; p.Jdirs = jdirs; p.out = out;
+    p.extra_out = est_out;
+    hipLaunchKernelGGL(k_track_joints, dim3((p.Tout + kTrackThreads - 1) / kTrackThreads, batch), dim3(kTrackThreads), 0, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
     return 0;
 }
 

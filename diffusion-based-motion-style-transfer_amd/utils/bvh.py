@@ -5,7 +5,8 @@ everything between is one launch for a batch of clips (csrc/mst_bvh.h): `decode_
 continuity of `remove_quat_discontinuities`, sub-sampling, `quat_fk`, joint selection) and `quats_to_channels` (`q2eul`, degrees, the
 writer's joint order).  `parse_bvh` and `format_bvh` need no GPU; nothing else here has a CPU path.
 
-Not covered: a fractional `downsample_rate` (the reference's slerp up-sampling; no caller in its tree), the nine-channel files,
+A fractional `downsample_rate` (the reference's slerp up-sampling) is `read_bvh_resampled`, over utils/pose_track.py's
+`resample_tracks`; `read_bvh`, `load_bvh` and `decode_channels` take whole rates only.  Not covered: the nine-channel files,
 `read_bvh_raw_motion` / `save_bvh_raw_motion`, and an `Anim` whose offsets include End Sites while its quaternions do not.
 
 Stated deviations from the reference's writer: it permutes the quaternions into its depth-first joint order but reads the positions (with
@@ -507,6 +508,34 @@ def read_bvh(filename, start=None, end=None, order=None, downsample_rate=None, e
         return anim(slice(None), sk.end_offsets)
     k = int(downsample_rate)
     return [anim(slice(i, None, k), None) for i in range(k)]
+
+
+def read_bvh_resampled(filename, downsample_rate, start=None, end=None, end_sites=False):
+    """The reference's `read_bvh` for a fractional `downsample_rate` (bvh_utils.py:251-287), e.g. 1.5 for a 30 fps file read at 20 fps: a
+    list of one `Anim` of numpy arrays, as there -- the local quaternions through `qslerp` and the local positions through `lerp`, both
+    float32, ceil((T - 1) * up / down) frames (the file's last frame is dropped, as there), without end_offsets.  The rate is read as the
+    reference's `decimal_to_fraction` reads it, from the number's own decimal text (1.5 -> 3/2); a `Fraction` or an (int, int) pair is taken
+    as it is.  The quaternions are made sign-continuous first (`decode_channels`), so the reference's formula (`shortest=False`) already
+    follows the shorter arc.  Global positions after the resampling are not formed: that is a forward-kinematics pass over the result."""
+    from fractions import Fraction
+    from . import pose_track as pt
+    what = "read_bvh_resampled"
+    if isinstance(downsample_rate, (Fraction, tuple, list)):
+        rate = pt.parse_rate(downsample_rate)
+    else:
+        rate = pt.parse_rate(pt.decimal_to_fraction(downsample_rate))
+    sk, ch = parse_bvh(filename, start, end)
+    if len(ch) < 2:
+        raise ValueError(f"{what}: {len(ch)} frame; a file is resampled interval by interval, so 2 frames at least")
+    if not torch.cuda.is_available():
+        raise RuntimeError(_NO_CPU.format(what))
+    m = decode_channels(torch.from_numpy(ch).cuda()[None], sk, return_local=True)
+    quats, pos, _ = pt.resample_tracks(m.rotations, m.local_positions, rate=rate, shortest=False)
+    quats, pos = quats[0].cpu().numpy(), pos[0].cpu().numpy()
+    if end_sites:
+        return [Anim(quats, pos, sk.offsets, np.array(sk.parents), list(sk.names))]
+    keep = sk.not_end_index
+    return [Anim(quats[:, keep], pos[:, keep], sk.offsets[keep], np.array(sk.simple_parents), sk.simple_names)]
 
 
 def quats_to_channels(quats, root_pos, parents, order="zyx", positions=None):

@@ -986,6 +986,43 @@ int mst_smplify_objective(int32_t stage, int32_t nj, int32_t frames, const float
                           float* grad_global_orient_dev, float* grad_betas_dev, float* grad_camera_translation_dev, float* rotations_dev,
                           void* stream);
 
+/* -----------------------------------------------------------------------------------------
+ * Pose tracks (csrc/mst_track.h): a video pose estimator's per-frame output -> joints at the model's frame rate.  Replaces
+ * `downsample`, `joints_downsample` and the frame loop of `amass_to_pose` (utils/process_smpl_from_hybrik.py:56-180) and the fractional
+ * branch of read_bvh (data_loaders/humanml/common/bvh_utils.py:251-287).  Stateless: one launch on `stream`, nothing allocated,
+ * nothing synchronised.  No atomics; a clip's outputs are the same bits alone, anywhere in a batch and on any stream, whatever other
+ * clips or the rows behind its length hold.
+ *
+ * The rate is the rational up / down: a clip of L source frames has the output frames k with k * down < (L - 1) * up -- the reference
+ * resamples intervals, so the source's last frame is dropped even at rate 1 -- taken from the interval i = (k * down) / up at
+ * t = ((k * down) % up) / up.  Outputs hold ceil((frames - 1) * up / down) rows a clip; rows at and behind a clip's own count are
+ * exact zeros.  lengths_dev [batch] int32 or NULL (every clip has `frames`); values are clamped to 1..frames.
+ *
+ * mst_track_resample: quats_dev [batch][frames][joints][4] (w first) through `qslerp` in float32 -- both ends normalised,
+ * qmul(q1, qinv(q0)), qpow with its 10e-10 guard, qmul with q0; shortest != 0 negates the relative quaternion when its w is negative --
+ * and points_dev [batch][frames][points][3] through p0 + t (p1 - p0) in double, stored as float32.  Either track may be absent (NULL
+ * with a count of 0).
+ * mst_track_joints: rotations_dev [batch][frames][rot_joints][4], or with is_matrix [..][3][3] (converted by the closed form of the
+ * reference's rotm2q, on the largest of the four diagonal combinations; the shorter arc is then always taken), resampled as above,
+ * `q2axangle`, Rodrigues (the form of mst_smplify_objective), J = j0_dev [22][3] + jdirs_dev [22][3][10] betas_dev [batch][10], the
+ * rigid chain over parents_host [22] -- only the first 22 joints of a frame are read -- plus the resampled transl_dev
+ * [batch][frames][3] under with_trans, re-axed (x and z swapped, y negated) into out_dev [batch][rows][22][3].  est_joints_dev
+ * [batch][frames][est_joint_count][3] (optional): the estimator's own joints through the same lerp, translation, re-axing and [:22]
+ * into est_out_dev.
+ * Refused without touching a device: batch < 1 (mst_track_joints: > 65535), frames outside 2..mst_track_max_frames, up or down outside
+ * 1..100000, a joint or point count outside its range, a count that disagrees with its pointer, an output that is its input, null
+ * operands, with_trans without transl_dev, parents[0] != -1 or a parents entry that is not an earlier joint.
+ * mst_track_max_frames: the longest source clip (16384); -1 for joints outside 1..4096.
+ * ----------------------------------------------------------------------------------------- */
+int mst_track_resample(const float* quats_dev, const float* points_dev, const int32_t* lengths_dev, int32_t batch, int32_t frames,
+                       int32_t joints, int32_t points, int32_t up, int32_t down, int32_t shortest, float* quats_out_dev,
+                       float* points_out_dev, void* stream);
+int mst_track_joints(const float* rotations_dev, int32_t is_matrix, int32_t rot_joints, const float* transl_dev, const float* betas_dev,
+                     const float* est_joints_dev, int32_t est_joint_count, const int32_t* lengths_dev, int32_t batch, int32_t frames,
+                     int32_t up, int32_t down, int32_t shortest, int32_t with_trans, const float* j0_dev, const float* jdirs_dev,
+                     const int32_t* parents_host, float* out_dev, float* est_out_dev, void* stream);
+int mst_track_max_frames(int32_t joints);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
