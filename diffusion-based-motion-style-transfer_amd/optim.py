@@ -8,6 +8,12 @@ import torch
 from . import _native as N
 
 
+def _need_gpu(dev):
+    """Apart from the checks of step() (which are host code), so that they can be run against a stub of the library."""
+    if dev.type != "cuda":
+        raise RuntimeError("FusedAdamW needs GPU parameters (the native kernel is the only implementation)")
+
+
 class FusedAdamW(torch.optim.AdamW):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, foreach=False, fused=False)
@@ -28,26 +34,30 @@ class FusedAdamW(torch.optim.AdamW):
             if not ps:
                 continue
             dev = ps[0].device
-            if dev.type != "cuda":
-                raise RuntimeError("FusedAdamW needs GPU parameters (the native kernel is the only implementation)")
+            _need_gpu(dev)
+            if len(self.param_groups) > 1:
+                raise NotImplementedError("FusedAdamW keeps one table workspace: a single parameter group")
+            # Every tensor is checked before anything changes: a refused call leaves the counters, the moments and the
+            # parameters as they were (a state created here starts at step 0, which is what it would have held anyway).
             steps = set()
             for p in ps:
+                if p.device != dev or p.grad.device != dev:
+                    raise RuntimeError("FusedAdamW: the parameters and gradients of one group live on one device")
+                if p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous() or p.grad.dtype != torch.float32:
+                    raise RuntimeError("FusedAdamW: float32 contiguous parameters and gradients only")
                 st = self.state[p]
                 if len(st) == 0:                                     # torch.optim.AdamW's lazy state, same keys / types
                     st["step"] = torch.tensor(0.0, dtype=torch.float32)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                if p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous() or p.grad.dtype != torch.float32:
-                    raise RuntimeError("FusedAdamW: float32 contiguous parameters and gradients only")
-                st["step"] += 1
-                steps.add(int(st["step"]))
+                steps.add(int(st["step"]) + 1)
             if len(steps) != 1:
                 raise RuntimeError("FusedAdamW: parameters of one group must share their step count")
+            for p in ps:
+                self.state[p]["step"] += 1
             n = len(ps)
             numel = (C.c_int64 * n)(*[p.numel() for p in ps])
             need = N.lib().mst_adamw_workspace_bytes(n, numel)
-            if len(self.param_groups) > 1:
-                raise NotImplementedError("FusedAdamW keeps one table workspace: a single parameter group")
             if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=dev)       # owned for the optimizer's lifetime
                 self._norms = torch.zeros(2, dtype=torch.float32, device=dev)
