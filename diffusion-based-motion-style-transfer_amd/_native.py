@@ -53,6 +53,20 @@ class MstClipWeights(C.Structure):
                [(n, C.c_void_p) for n in ("tok_emb", "pos_emb", "lnf_g", "lnf_b", "proj")] + [("layer", C.POINTER(MstClipLayer))]
 
 
+class MstRenderScene(C.Structure):
+    _fields_ = [("joints_dev", C.c_void_p), ("joints2_dev", C.c_void_p), ("stride_batch", C.c_int64), ("stride_frame", C.c_int64),
+                ("stride_joint", C.c_int64), ("stride_coord", C.c_int64), ("lengths_dev", C.c_void_p), ("batch", C.c_int32),
+                ("frames", C.c_int32), ("joints", C.c_int32), ("scale", C.c_float)]
+
+
+class MstRenderView(C.Structure):
+    _fields_ = [("n_chains", C.c_int32), ("chain_offsets_host", C.POINTER(C.c_int32)), ("chain_joints_host", C.POINTER(C.c_int32)),
+                ("n_traces", C.c_int32), ("trace_kinds_host", C.POINTER(C.c_int32)), ("trace_joints_host", C.POINTER(C.c_int32)),
+                ("palette_dev", C.c_void_p), ("proj", C.c_float * 16), ("affine", C.c_float * 6), ("width", C.c_int32),
+                ("height", C.c_int32), ("dpi", C.c_float), ("overlay_dev", C.c_void_p), ("overlay_batch", C.c_int32), ("t0", C.c_int32),
+                ("t1", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every function include/mst_engine.h declares
 SIGNATURES = {
     "mst_last_error": (C.c_char_p, []),
@@ -210,6 +224,14 @@ SIGNATURES = {
                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "mst_track_max_frames": (C.c_int, [C.c_int32]),
+    "mst_render_bounds": (C.c_int, [C.POINTER(MstRenderScene), C.c_void_p, C.c_void_p]),
+    "mst_render_frames": (C.c_int, [C.POINTER(MstRenderScene), C.c_void_p, C.POINTER(MstRenderView), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mst_render_max_frames": (C.c_int, []),
+    "mst_render_max_joints": (C.c_int, []),
+    "mst_render_chains_drawn": (C.c_int, []),
+    "mst_render_max_traces": (C.c_int, []),
+    "mst_render_max_side": (C.c_int, []),
+    "mst_render_chunk": (C.c_int, []),
     "mst_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "mst_profile_event_overhead_us": (C.c_float, [C.c_void_p]),
     "mst_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(C.c_int32),

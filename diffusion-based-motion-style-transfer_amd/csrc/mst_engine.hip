@@ -43,6 +43,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_smpl.h"
 #include "mst_smplify.h"
 #include "mst_track.h"
+#include "mst_render.h"
 
 using namespace mst;
 
@@ -4077,6 +4078,98 @@ extern "C" int mst_track_joints(const float* rotations, int32_t is_matrix, int32
     p.up = up; p.down = down; p.shortest = shortest != 0; p.with_trans = with_trans != 0; p.J0 = j0; p.Jdirs = jdirs; p.out = out;
     p.extra_out = est_out;
     hipLaunchKernelGGL(k_track_joints, dim3((p.Tout + kTrackThreads - 1) / kTrackThreads, batch), dim3(kTrackThreads), 0, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ clips to video frames (mst_render.h)
+extern "C" int mst_render_max_frames(void) { return kRenderMaxFrames; }
+extern "C" int mst_render_max_joints(void) { return kRenderMaxJoints; }
+extern "C" int mst_render_chains_drawn(void) { return kRenderChains; }
+extern "C" int mst_render_max_traces(void) { return kRenderMaxTraces; }
+extern "C" int mst_render_max_side(void) { return kRenderMaxSide; }
+extern "C" int mst_render_chunk(void) { return kRenderChunk; }
+
+static int render_scene(const char* what, const mst_render_scene* s, RenderArgs& p) {
+    if (!s) return fail("%s: null scene", what);
+    if (s->batch < 1 || s->batch > 65535) return fail("%s: batch %d outside 1..65535", what, s->batch);
+    if (s->frames < 1 || s->frames > kRenderMaxFrames) return fail("%s: frames %d outside 1..%d (mst_render_max_frames)", what, s->frames, kRenderMaxFrames);
+    if (s->joints < 1 || s->joints > kRenderMaxJoints) return fail("%s: joints %d outside 1..%d (mst_render_max_joints)", what, s->joints, kRenderMaxJoints);
+    if (!s->joints_dev) return fail("%s: null joints", what);
+    if (s->stride_batch < 1 || s->stride_frame < 1 || s->stride_joint < 1 || s->stride_coord < 1)
+        return fail("%s: strides %lld, %lld, %lld, %lld: each at least 1 element", what, (long long)s->stride_batch, (long long)s->stride_frame,
+                    (long long)s->stride_joint, (long long)s->stride_coord);
+    if (!(s->scale == s->scale) || s->scale - s->scale != 0.f) return fail("%s: scale is not finite", what);
+    p.joints = s->joints_dev; p.joints2 = s->joints2_dev; p.sB = s->stride_batch; p.sT = s->stride_frame; p.sJ = s->stride_joint;
+    p.sC = s->stride_coord; p.lengths = s->lengths_dev; p.B = s->batch; p.T = s->frames; p.J = s->joints; p.scale = s->scale;
+    return 0;
+}
+
+extern "C" int mst_render_bounds(const mst_render_scene* scene, float* bounds, void* stream) {
+    RenderArgs p{};
+    CHECK(render_scene("mst_render_bounds", scene, p));
+    if (!bounds) return fail("mst_render_bounds: null bounds");
+    if ((const void*)bounds == (const void*)p.joints || (const void*)bounds == (const void*)p.joints2 || (const void*)bounds == (const void*)p.lengths)
+        return fail("mst_render_bounds: the output may not be an input");
+    hipLaunchKernelGGL(k_render_bounds, dim3(p.B), dim3(kRenderThreads), 0, (hipStream_t)stream, p, bounds);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_render_frames(const mst_render_scene* scene, const float* bounds, const mst_render_view* v, uint8_t* out, float* out_float,
+                                 void* stream) {
+    const char* what = "mst_render_frames";
+    RenderArgs p{};
+    CHECK(render_scene(what, scene, p));
+    if (!v) return fail("%s: null view", what);
+    if (!bounds || !out) return fail("%s: null bounds or output", what);
+    if (v->width < kRenderMinSide || v->width > kRenderMaxSide || v->height < kRenderMinSide || v->height > kRenderMaxSide)
+        return fail("%s: image %d x %d: each side %d..%d (mst_render_max_side)", what, v->width, v->height, kRenderMinSide, kRenderMaxSide);
+    if (v->n_chains < 0 || v->n_chains > kRenderMaxChains) return fail("%s: %d chains outside 0..%d", what, v->n_chains, kRenderMaxChains);
+    if (v->n_chains > 0 && (!v->chain_offsets_host || !v->chain_joints_host)) return fail("%s: %d chains but null chain tables", what, v->n_chains);
+    if (v->n_chains > 0 && v->chain_offsets_host[0] != 0) return fail("%s: chain offsets start at %d, not 0", what, v->chain_offsets_host[0]);
+    for (int c = 0; c < v->n_chains; c++) {
+        const int o = v->chain_offsets_host[c], e = v->chain_offsets_host[c + 1];
+        if (e < o || e - o > kRenderMaxChainPoints) return fail("%s: chain %d holds %d points, outside 0..%d", what, c, e - o, kRenderMaxChainPoints);
+        for (int i = o; i < e; i++)
+            if (v->chain_joints_host[i] < 0 || v->chain_joints_host[i] >= p.J)
+                return fail("%s: chain %d names joint %d, outside 0..%d", what, c, v->chain_joints_host[i], p.J - 1);
+    }
+    p.n_chains = v->n_chains < kRenderChains ? v->n_chains : kRenderChains;     // every chain is checked, the first five are drawn
+    if (p.n_chains > 0 && v->chain_offsets_host[p.n_chains] > kRenderMaxChainPoints)
+        return fail("%s: the %d chains drawn hold %d points, more than %d", what, p.n_chains, v->chain_offsets_host[p.n_chains], kRenderMaxChainPoints);
+    for (int c = 0; c <= p.n_chains; c++) p.chain_off[c] = (unsigned char)(p.n_chains ? v->chain_offsets_host[c] : 0);
+    for (int i = 0; i < p.chain_off[p.n_chains]; i++) p.chain_joint[i] = (unsigned char)v->chain_joints_host[i];
+    if (v->n_traces < 0 || v->n_traces > kRenderMaxTraces) return fail("%s: %d traces outside 0..%d (mst_render_max_traces)", what, v->n_traces, kRenderMaxTraces);
+    if (v->n_traces > 0 && (!v->trace_kinds_host || !v->trace_joints_host)) return fail("%s: %d traces but null trace tables", what, v->n_traces);
+    for (int i = 0; i < v->n_traces; i++) {
+        if (v->trace_kinds_host[i] < 0 || v->trace_kinds_host[i] > 2) return fail("%s: trace %d of kind %d, outside 0..2", what, i, v->trace_kinds_host[i]);
+        if (v->trace_joints_host[i] < 0 || v->trace_joints_host[i] >= p.J)
+            return fail("%s: trace %d names joint %d, outside 0..%d", what, i, v->trace_joints_host[i], p.J - 1);
+        p.trace_kind[i] = (unsigned char)v->trace_kinds_host[i];
+        p.trace_joint[i] = (unsigned char)v->trace_joints_host[i];
+    }
+    p.n_traces = v->n_traces;
+    if (v->overlay_dev && v->overlay_batch != 1 && v->overlay_batch != p.B)
+        return fail("%s: an overlay of %d images for %d clips: 1 or the batch", what, v->overlay_batch, p.B);
+    if (!(v->t0 >= 0 && v->t0 < v->t1 && v->t1 <= p.T)) return fail("%s: frame range %d..%d is not 0 <= t0 < t1 <= %d", what, v->t0, v->t1, p.T);
+    if (!(v->dpi > 0.f) || v->dpi - v->dpi != 0.f) return fail("%s: dpi is not a positive finite number", what);
+    const void* ins[] = {p.joints, p.joints2, p.lengths, bounds, v->palette_dev, v->overlay_dev};
+    for (const void* in : ins)
+        if (in && (in == (const void*)out || in == (const void*)out_float)) return fail("%s: an output may not be an input", what);
+    if ((const void*)out == (const void*)out_float) return fail("%s: the two outputs may not be one buffer", what);
+    p.bounds = bounds; p.palette = v->palette_dev;
+    for (int r = 0; r < 2; r++)
+        for (int c = 0; c < 4; c++) p.M[4 * r + c] = v->proj[4 * r + c];
+    for (int c = 0; c < 4; c++) p.M[8 + c] = v->proj[12 + c];                  // the depth row is not read: nothing is depth-tested
+    for (int i = 0; i < 6; i++) p.A[i] = v->affine[i];
+    p.W = v->width; p.H = v->height;
+    // line widths of 4 pt and 2 pt: w = pt * dpi / 72 pixels formed in double and rounded once, the reach w / 2 + 0.5 in float32
+    const float w_chain = (float)(4.0 * (double)v->dpi / 72.0), w_trace = (float)(2.0 * (double)v->dpi / 72.0);
+    p.reach_chain = w_chain * 0.5f + 0.5f; p.reach_trace = w_trace * 0.5f + 0.5f;
+    p.overlay = v->overlay_dev; p.overlay_batch = v->overlay_batch; p.t0 = v->t0; p.frames_out = v->t1 - v->t0; p.out = out; p.outf = out_float;
+    const int tiles = ((p.W + kRenderTile - 1) / kRenderTile) * ((p.H + kRenderTile - 1) / kRenderTile);
+    hipLaunchKernelGGL(k_render_frames, dim3(tiles, p.frames_out, p.B), dim3(kRenderThreads), 0, (hipStream_t)stream, p);
     HIPCHECK(hipGetLastError());
     return 0;
 }

@@ -1023,6 +1023,82 @@ int mst_track_joints(const float* rotations_dev, int32_t is_matrix, int32_t rot_
                      const int32_t* parents_host, float* out_dev, float* est_out_dev, void* stream);
 int mst_track_max_frames(int32_t joints);
 
+/* -----------------------------------------------------------------------------------------
+ * Clips to video frames (csrc/mst_render.h): joints -> [batch][frames][height][width][3] uint8 images of the stick figure over its
+ * ground plane, with root or joint traces.  Replaces the per-frame matplotlib redraw of `explicit_plot_3d_motion`
+ * (data_loaders/humanml/utils/plot_script.py:168-311): its scene, drawn by the rules below, not by matplotlib's rasteriser.
+ * Stateless: one launch each on `stream`, nothing allocated, nothing synchronised.  No atomics; a clip's frames are the same bits
+ * alone, anywhere in a batch, on any stream and for any frame sub-range, whatever other clips or the frames behind its length hold.
+ * Frames at and behind a clip's length are exact zeros.  All arithmetic is float32 without fused multiply-adds.
+ *
+ * mst_render_scene: joints_dev element (b, t, j, c) lies at b * stride_batch + t * stride_frame + j * stride_joint + c * stride_coord
+ * (elements; [B][T][J][3] and [B][J][3][T] are both a choice of strides); joints2_dev (optional) is a second skeleton with the same
+ * strides; lengths_dev [batch] int32 or NULL (every clip has `frames`), clamped to 1..frames.
+ *
+ * mst_render_bounds (:221-225, :243): bounds_dev [batch][8] = MINS xyz, MAXS xyz of scale * joints over the clip's live frames, all
+ * joints and both skeletons, then two zeros.  Minimum and maximum pass over NaN (fmin / fmax).
+ *
+ * mst_render_frames (:257-305), frame t of a clip, everything relative to (traj[t].x, 0, traj[t].z), traj[t] = scale * joints[t, 0]:
+ *   W[k, j] = scale * joints[k, j] with y -= MINS.y; a point of frame k seen from frame t is W[k, j] - (traj[t].x, 0, traj[t].z).
+ *   Ground quad: (MINS.x, 0, MINS.z), (MINS.x, 0, MAXS.z), (MAXS.x, 0, MAXS.z), (MAXS.x, 0, MINS.z), each minus traj[t] in x and z;
+ *     0.5 grey at alpha 0.5; coverage clamp(0.5 + min over the edges of the signed distance, 0, 1) in pixels, the sign from the
+ *     quad's area; an edge of no length is passed over; coverage 0 where |area| < 1e-12 px^2 or a corner is not drawn.
+ *   Chains: the first mst_render_chains_drawn() (5: the reference's zip with a five-colour palette stops there) of the chains given,
+ *     each one polyline of width 4 pt in colour [palette][chain]; with joints2 its chain right after the first skeleton's same chain,
+ *     in the same colour.  palette_dev [batch][frames] int32 (0 blue, 1 orange, 2 purple, 3 upper_body; NULL: orange; clamped).
+ *   Traces, each one polyline of width 2 pt in colour [palette][0]: kind 0 (root_horizontal) joint 0 at frames k < t with y = 0,
+ *     kind 1 (root) joint 0 at k < t, kind 2 joint trace_joints[i] at k <= t.  Fewer than 2 points draw nothing.
+ *   Polyline coverage: clamp((w / 2 + 0.5) - d, 0, 1), w = pt * dpi / 72 pixels, d the minimum over the polyline's segments of the
+ *     distance from the pixel centre to the segment (parameter clamped to [0, 1], a segment of no length is a point).  A point is not
+ *     drawn when a coordinate is not finite or its projective w is not positive and finite; a segment with such an end is skipped.
+ *     One polyline is one layer.
+ *   Projection: (X, Y, . , w) = proj (x, y, z, 1) (row-major 4 x 4; the depth row is not read), pixels = affine (X / w, Y / w, 1)
+ *     (row-major 2 x 3), y up: pixel (row, col) has its centre at (col + 0.5, height - row - 0.5).
+ *   Compositing: straight-alpha over, c = c (1 - a) + colour a, on white, in the order quad, chains, traces, then overlay_dev
+ *     [overlay_batch = 1 or batch][height][width] uint8 (optional) as coverage / 255 in black.  out_dev = floor(255 c + 0.5);
+ *     out_float_dev (optional) is c itself in the same layout.  Frames t0 <= t < t1 are rendered into t1 - t0 output frames; traces
+ *     still reach back to frame 0.
+ * Refused without touching a device: a null scene, view, joints, bounds or output; batch outside 1..65535; frames outside
+ * 1..mst_render_max_frames (4096); joints outside 1..mst_render_max_joints (64); a stride below 1; a scale or dpi that is not finite
+ * (dpi: and positive); width or height outside 16..mst_render_max_side (1024); more than 16 chains, or more than 128 points in the
+ * chains drawn; a chain or trace joint outside 0..joints-1; a trace kind outside 0..2; more than mst_render_max_traces (8) traces;
+ * an overlay batch that is neither 1 nor batch; a range that is not 0 <= t0 < t1 <= frames; an output that is an input or the other
+ * output.  mst_render_chunk: the polyline points a workgroup holds on chip at a time (512).
+ * ----------------------------------------------------------------------------------------- */
+typedef struct mst_render_scene {
+    const float* joints_dev;
+    const float* joints2_dev;
+    int64_t stride_batch, stride_frame, stride_joint, stride_coord;
+    const int32_t* lengths_dev;
+    int32_t batch, frames, joints;
+    float scale;
+} mst_render_scene;
+typedef struct mst_render_view {
+    int32_t n_chains;
+    const int32_t* chain_offsets_host;        /* [n_chains + 1], from 0 */
+    const int32_t* chain_joints_host;
+    int32_t n_traces;
+    const int32_t* trace_kinds_host;          /* [n_traces] */
+    const int32_t* trace_joints_host;         /* [n_traces]; read for kind 2 */
+    const int32_t* palette_dev;
+    float proj[16];
+    float affine[6];
+    int32_t width, height;
+    float dpi;
+    const uint8_t* overlay_dev;
+    int32_t overlay_batch;
+    int32_t t0, t1;
+} mst_render_view;
+int mst_render_bounds(const mst_render_scene* scene_host, float* bounds_dev, void* stream);
+int mst_render_frames(const mst_render_scene* scene_host, const float* bounds_dev, const mst_render_view* view_host, uint8_t* out_dev,
+                      float* out_float_dev, void* stream);
+int mst_render_max_frames(void);
+int mst_render_max_joints(void);
+int mst_render_chains_drawn(void);
+int mst_render_max_traces(void);
+int mst_render_max_side(void);
+int mst_render_chunk(void);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
