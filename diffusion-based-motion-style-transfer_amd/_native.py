@@ -67,6 +67,20 @@ class MstRenderView(C.Structure):
                 ("t1", C.c_int32)]
 
 
+class MstMeshScene(C.Structure):
+    _fields_ = [("vertices_dev", C.c_void_p), ("stride_batch", C.c_int64), ("stride_frame", C.c_int64), ("stride_vertex", C.c_int64),
+                ("stride_coord", C.c_int64), ("lengths_dev", C.c_void_p), ("batch", C.c_int32), ("frames", C.c_int32),
+                ("vertices", C.c_int32), ("faces", C.c_int32), ("faces_host", C.c_void_p), ("faces_dev", C.c_void_p),
+                ("adj_offsets_host", C.c_void_p), ("adj_offsets_dev", C.c_void_p), ("adj_faces_host", C.c_void_p),
+                ("adj_faces_dev", C.c_void_p)]
+
+
+class MstMeshView(C.Structure):
+    _fields_ = [("proj_host", C.c_void_p), ("proj_dev", C.c_void_p), ("proj_batch", C.c_int32), ("affine", C.c_float * 6),
+                ("width", C.c_int32), ("height", C.c_int32), ("samples", C.c_int32), ("light", C.c_float * 3), ("ambient", C.c_float),
+                ("colors_dev", C.c_void_p), ("background", C.c_float * 4), ("t0", C.c_int32), ("t1", C.c_int32), ("ids_sample", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every function include/mst_engine.h declares
 SIGNATURES = {
     "mst_last_error": (C.c_char_p, []),
@@ -232,6 +246,16 @@ SIGNATURES = {
     "mst_render_max_traces": (C.c_int, []),
     "mst_render_max_side": (C.c_int, []),
     "mst_render_chunk": (C.c_int, []),
+    "mst_mesh_bounds": (C.c_int, [C.POINTER(MstMeshScene), C.c_void_p, C.c_void_p]),
+    "mst_mesh_vertices": (C.c_int, [C.POINTER(MstMeshScene), C.POINTER(MstMeshView), C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mst_mesh_frames": (C.c_int, [C.POINTER(MstMeshScene), C.POINTER(MstMeshView), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    "mst_mesh_workspace_bytes": (C.c_uint64, [C.c_int32, C.c_int32, C.c_int32]),
+    "mst_mesh_max_vertices": (C.c_int, []),
+    "mst_mesh_max_faces": (C.c_int, []),
+    "mst_mesh_max_side": (C.c_int, []),
+    "mst_mesh_max_samples": (C.c_int, []),
+    "mst_mesh_chunk": (C.c_int, []),
     "mst_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
     "mst_profile_event_overhead_us": (C.c_float, [C.c_void_p]),
     "mst_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(C.c_int32),

@@ -44,6 +44,7 @@ extern "C" int mst_probe_read(void* dst) { return hipMemcpyFromSymbol(dst, HIP_S
 #include "mst_smplify.h"
 #include "mst_track.h"
 #include "mst_render.h"
+#include "mst_mesh.h"
 
 using namespace mst;
 
@@ -4170,6 +4171,134 @@ extern "C" int mst_render_frames(const mst_render_scene* scene, const float* bou
     p.overlay = v->overlay_dev; p.overlay_batch = v->overlay_batch; p.t0 = v->t0; p.frames_out = v->t1 - v->t0; p.out = out; p.outf = out_float;
     const int tiles = ((p.W + kRenderTile - 1) / kRenderTile) * ((p.H + kRenderTile - 1) / kRenderTile);
     hipLaunchKernelGGL(k_render_frames, dim3(tiles, p.frames_out, p.B), dim3(kRenderThreads), 0, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ meshes to video frames (mst_mesh.h)
+extern "C" int mst_mesh_max_vertices(void) { return kMeshMaxVertices; }
+extern "C" int mst_mesh_max_faces(void) { return kMeshMaxFaces; }
+extern "C" int mst_mesh_max_side(void) { return kMeshMaxSide; }
+extern "C" int mst_mesh_max_samples(void) { return kMeshMaxSamples; }
+extern "C" int mst_mesh_chunk(void) { return kMeshChunk; }
+
+extern "C" uint64_t mst_mesh_workspace_bytes(int32_t batch, int32_t frames_out, int32_t vertices) {
+    if (batch < 1 || frames_out < 1 || vertices < 1 || vertices > kMeshMaxVertices) return 0;
+    return (uint64_t)batch * (uint64_t)frames_out * (uint64_t)mesh_frame_floats(vertices) * sizeof(float);
+}
+
+static bool mesh_finite(const float* a, int n) {
+    for (int i = 0; i < n; i++)
+        if (!(a[i] - a[i] == 0.f)) return false;
+    return true;
+}
+
+static int mesh_scene(const char* what, const mst_mesh_scene* s, bool topology, MeshArgs& p) {
+    if (!s) return fail("%s: null scene", what);
+    if (s->batch < 1 || s->batch > 65535) return fail("%s: batch %d outside 1..65535", what, s->batch);
+    if (s->frames < 1 || s->frames > kMeshMaxFrames) return fail("%s: frames %d outside 1..%d", what, s->frames, kMeshMaxFrames);
+    if (s->vertices < 1 || s->vertices > kMeshMaxVertices)
+        return fail("%s: vertices %d outside 1..%d (mst_mesh_max_vertices)", what, s->vertices, kMeshMaxVertices);
+    if (!s->vertices_dev) return fail("%s: null vertices", what);
+    if (s->stride_batch < 1 || s->stride_frame < 1 || s->stride_vertex < 1 || s->stride_coord < 1)
+        return fail("%s: strides %lld, %lld, %lld, %lld: each at least 1 element", what, (long long)s->stride_batch, (long long)s->stride_frame,
+                    (long long)s->stride_vertex, (long long)s->stride_coord);
+    p.verts = s->vertices_dev; p.sB = s->stride_batch; p.sT = s->stride_frame; p.sV = s->stride_vertex; p.sC = s->stride_coord;
+    p.lengths = s->lengths_dev; p.B = s->batch; p.T = s->frames; p.V = s->vertices;
+    if (!topology) return 0;
+    const int V = s->vertices, F = s->faces;
+    if (F < 1 || F > kMeshMaxFaces) return fail("%s: faces %d outside 1..%d (mst_mesh_max_faces)", what, F, kMeshMaxFaces);
+    if (!s->faces_host || !s->faces_dev) return fail("%s: null faces (a host copy and a device copy)", what);
+    if (!s->adj_offsets_host || !s->adj_offsets_dev || !s->adj_faces_host || !s->adj_faces_dev)
+        return fail("%s: null adjacency (host and device copies of the offsets and of the face lists)", what);
+    for (int i = 0; i < 3 * F; i++)
+        if (s->faces_host[i] < 0 || s->faces_host[i] >= V)
+            return fail("%s: face %d names vertex %d, outside 0..%d", what, i / 3, s->faces_host[i], V - 1);
+    if (s->adj_offsets_host[0] != 0 || s->adj_offsets_host[V] != 3 * F)
+        return fail("%s: adjacency rows sum to %d from %d, not to 3 x faces = %d from 0", what, s->adj_offsets_host[V], s->adj_offsets_host[0], 3 * F);
+    for (int v = 0; v < V; v++)
+        if (s->adj_offsets_host[v + 1] < s->adj_offsets_host[v]) return fail("%s: adjacency offsets fall at vertex %d", what, v);
+    for (int i = 0; i < 3 * F; i++)
+        if (s->adj_faces_host[i] < 0 || s->adj_faces_host[i] >= F)
+            return fail("%s: adjacency entry %d names face %d, outside 0..%d", what, i, s->adj_faces_host[i], F - 1);
+    p.F = F; p.faces = s->faces_dev; p.adj_off = s->adj_offsets_dev; p.adj_face = s->adj_faces_dev;
+    return 0;
+}
+
+static int mesh_view(const char* what, const mst_mesh_view* v, void* ws, uint64_t ws_bytes, MeshArgs& p) {
+    if (!v) return fail("%s: null view", what);
+    if (!v->proj_host || !v->proj_dev) return fail("%s: null matrix (a host copy and a device copy)", what);
+    if (v->proj_batch != 1 && v->proj_batch != p.B) return fail("%s: %d matrices for %d clips: 1 or the batch", what, v->proj_batch, p.B);
+    if (!mesh_finite(v->proj_host, 16 * v->proj_batch) || !mesh_finite(v->affine, 6)) return fail("%s: a matrix or the affine is not finite", what);
+    if (v->width < kMeshMinSide || v->width > kMeshMaxSide || v->height < kMeshMinSide || v->height > kMeshMaxSide)
+        return fail("%s: image %d x %d: each side %d..%d (mst_mesh_max_side)", what, v->width, v->height, kMeshMinSide, kMeshMaxSide);
+    if (v->samples < 1 || v->samples > kMeshMaxSamples) return fail("%s: samples %d outside 1..%d (mst_mesh_max_samples)", what, v->samples, kMeshMaxSamples);
+    if (v->ids_sample < 0 || v->ids_sample >= v->samples * v->samples)
+        return fail("%s: ids_sample %d outside 0..%d", what, v->ids_sample, v->samples * v->samples - 1);
+    if (!mesh_finite(v->light, 3) || !mesh_finite(&v->ambient, 1) || !mesh_finite(v->background, 4))
+        return fail("%s: the light, ambient or background is not finite", what);
+    if (!(v->t0 >= 0 && v->t0 < v->t1 && v->t1 <= p.T)) return fail("%s: frame range %d..%d is not 0 <= t0 < t1 <= %d", what, v->t0, v->t1, p.T);
+    if (!ws) return fail("%s: null workspace", what);
+    const uint64_t need = mst_mesh_workspace_bytes(p.B, v->t1 - v->t0, p.V);
+    if (ws_bytes < need)
+        return fail("%s: workspace of %llu bytes, mst_mesh_workspace_bytes says %llu", what, (unsigned long long)ws_bytes, (unsigned long long)need);
+    if (((uintptr_t)ws & 3) != 0) return fail("%s: the workspace is not 4-byte aligned", what);
+    p.proj = v->proj_dev; p.proj_batch = v->proj_batch;
+    for (int i = 0; i < 6; i++) p.A[i] = v->affine[i];
+    p.W = v->width; p.H = v->height;
+    for (int i = 0; i < 3; i++) p.light[i] = v->light[i];
+    p.ambient = v->ambient; p.colors = v->colors_dev;
+    for (int i = 0; i < 4; i++) p.bg[i] = v->background[i];
+    p.t0 = v->t0; p.frames_out = v->t1 - v->t0; p.ids_sample = v->ids_sample; p.ws = (float*)ws;
+    return 0;
+}
+
+extern "C" int mst_mesh_bounds(const mst_mesh_scene* scene, float* bounds, void* stream) {
+    MeshArgs p{};
+    CHECK(mesh_scene("mst_mesh_bounds", scene, false, p));
+    if (!bounds) return fail("mst_mesh_bounds: null bounds");
+    if ((const void*)bounds == (const void*)p.verts || (const void*)bounds == (const void*)p.lengths)
+        return fail("mst_mesh_bounds: the output may not be an input");
+    hipLaunchKernelGGL(k_mesh_bounds, dim3(p.B), dim3(kMeshThreads), 0, (hipStream_t)stream, p, bounds);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_mesh_vertices(const mst_mesh_scene* scene, const mst_mesh_view* view, void* workspace, uint64_t workspace_bytes, void* stream) {
+    const char* what = "mst_mesh_vertices";
+    MeshArgs p{};
+    CHECK(mesh_scene(what, scene, true, p));
+    CHECK(mesh_view(what, view, workspace, workspace_bytes, p));
+    const void* ins[] = {p.verts, p.lengths, p.faces, p.adj_off, p.adj_face, p.proj, p.colors};
+    for (const void* in : ins)
+        if (in && in == (const void*)workspace) return fail("%s: the workspace may not be an input", what);
+    hipLaunchKernelGGL(k_mesh_vertices, dim3(mesh_blocks(p.V), p.frames_out, p.B), dim3(kMeshThreads), 0, (hipStream_t)stream, p);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mst_mesh_frames(const mst_mesh_scene* scene, const mst_mesh_view* view, const void* workspace, uint64_t workspace_bytes, uint8_t* out,
+                               float* out_float, int32_t* out_ids, void* stream) {
+    const char* what = "mst_mesh_frames";
+    MeshArgs p{};
+    CHECK(mesh_scene(what, scene, true, p));
+    CHECK(mesh_view(what, view, const_cast<void*>(workspace), workspace_bytes, p));
+    if (!out) return fail("%s: null output", what);
+    if (((uintptr_t)out & 3) != 0 || ((uintptr_t)out_float & 15) != 0 || ((uintptr_t)out_ids & 3) != 0)
+        return fail("%s: the image is 4-byte aligned, the float image 16-byte, the face-index image 4-byte", what);
+    const void* ins[] = {p.verts, p.lengths, p.faces, p.adj_off, p.adj_face, p.proj, p.colors, workspace};
+    for (const void* in : ins)
+        if (in && (in == (const void*)out || in == (const void*)out_float || in == (const void*)out_ids)) return fail("%s: an output may not be an input", what);
+    if ((const void*)out == (const void*)out_float || (const void*)out == (const void*)out_ids || (out_float && (const void*)out_float == (const void*)out_ids))
+        return fail("%s: the outputs may not share a buffer", what);
+    p.out = out; p.outf = out_float; p.ids = out_ids;
+    const dim3 grid(((p.W + kMeshTile - 1) / kMeshTile) * ((p.H + kMeshTile - 1) / kMeshTile), p.frames_out, p.B), block(kMeshThreads);
+    switch (view->samples) {
+        case 1: hipLaunchKernelGGL(k_mesh_frames<1>, grid, block, 0, (hipStream_t)stream, p); break;
+        case 2: hipLaunchKernelGGL(k_mesh_frames<2>, grid, block, 0, (hipStream_t)stream, p); break;
+        case 3: hipLaunchKernelGGL(k_mesh_frames<3>, grid, block, 0, (hipStream_t)stream, p); break;
+        default: hipLaunchKernelGGL(k_mesh_frames<4>, grid, block, 0, (hipStream_t)stream, p); break;
+    }
     HIPCHECK(hipGetLastError());
     return 0;
 }

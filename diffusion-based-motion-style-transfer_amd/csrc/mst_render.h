@@ -77,22 +77,9 @@ __device__ __forceinline__ int render_len(const RenderArgs& p, int b) {
 }
 
 // ------------------------------------------------------------------------------------------ MINS / MAXS
-__global__ __launch_bounds__(kRenderThreads) void k_render_bounds(const RenderArgs p, float* __restrict__ bounds) {
-#pragma clang fp contract(off)
-    __shared__ float s_red[kRenderThreads / 64][6];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = render_len(p, b) * p.J, total = p.joints2 ? 2 * n : n;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = tid; i < total; i += kRenderThreads) {
-        const int r = i < n ? i : i - n, k = r / p.J, j = r - k * p.J;
-        const float* s = (i < n ? p.joints : p.joints2) + (long long)b * p.sB + (long long)k * p.sT + (long long)j * p.sJ;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float v = p.scale * s[c * p.sC];
-            mn[c] = fminf(mn[c], v);         // NaN is passed over, as numpy's fmin / fmax do
-            mx[c] = fmaxf(mx[c], v);
-        }
-    }
+// the workgroup's minimum and maximum of three coordinates -> out[8]: MINS xyz, MAXS xyz, two zeros (shared with mst_mesh.h)
+__device__ __forceinline__ void render_bounds_reduce(float* mn, float* mx, float (*s_red)[6], float* __restrict__ out) {
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         for (int o = 32; o > 0; o >>= 1) {
@@ -114,8 +101,27 @@ __global__ __launch_bounds__(kRenderThreads) void k_render_bounds(const RenderAr
             v = s_red[0][tid];
             for (int w = 1; w < kRenderThreads / 64; w++) v = tid < 3 ? fminf(v, s_red[w][tid]) : fmaxf(v, s_red[w][tid]);
         }
-        bounds[(size_t)b * 8 + tid] = v;
+        out[tid] = v;
     }
+}
+
+__global__ __launch_bounds__(kRenderThreads) void k_render_bounds(const RenderArgs p, float* __restrict__ bounds) {
+#pragma clang fp contract(off)
+    __shared__ float s_red[kRenderThreads / 64][6];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = render_len(p, b) * p.J, total = p.joints2 ? 2 * n : n;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = tid; i < total; i += kRenderThreads) {
+        const int r = i < n ? i : i - n, k = r / p.J, j = r - k * p.J;
+        const float* s = (i < n ? p.joints : p.joints2) + (long long)b * p.sB + (long long)k * p.sT + (long long)j * p.sJ;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float v = p.scale * s[c * p.sC];
+            mn[c] = fminf(mn[c], v);         // NaN is passed over, as numpy's fmin / fmax do
+            mx[c] = fmaxf(mx[c], v);
+        }
+    }
+    render_bounds_reduce(mn, mx, s_red, bounds + (size_t)b * 8);
 }
 
 // ------------------------------------------------------------------------------------------ frames

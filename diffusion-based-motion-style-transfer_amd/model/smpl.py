@@ -122,6 +122,14 @@ class SMPLBody:
         self.device = torch.device(device)
         self._dev = {}                                    # device -> the uploaded arrays, made on first use there
 
+    @property
+    def topology(self):
+        """The faces and their vertex -> faces adjacency as `visualize.mesh_render.render_meshes` reads them, built once."""
+        if getattr(self, "_topology", None) is None:
+            from ..visualize.mesh_render import MeshTopology
+            self._topology = MeshTopology(self.faces, self.num_vertices)
+        return self._topology
+
     # ------------------------------------------------------------------ constructors
     @classmethod
     def from_arrays(cls, *, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, faces, J_regressor_extra, vertex_ids,
@@ -258,6 +266,10 @@ class SMPL:
         self.body = body
         self.faces = body.faces
         self.maps = joint_maps()
+
+    @property
+    def topology(self):
+        return self.body.topology
 
     def eval(self):
         return self

@@ -430,7 +430,8 @@ def render_to_file(path, joints, kinematic_tree, fps=20, chunk=32, **kw):
 
 
 def save_frames(path, frames, fps=20, chunk=32):
-    """frames uint8 [T, H, W, 3] (a tensor on any device, or numpy) -> a file chosen by the extension: .npy (always), .gif and .png
+    """frames uint8 [T, H, W, 3] (a tensor on any device, or numpy; [T, H, W, 4] RGBA too: .npy and .png keep the alpha channel,
+    .gif and .mp4 drop it and write the colours as they are) -> a file chosen by the extension: .npy (always), .gif and .png
     (numbered files path_0000.png ...) through PIL, .mp4 as raw RGB piped to an `ffmpeg` found on PATH (FfmpegNotFound when there is
     none; nothing is bundled or fetched).  Frames come to the host `chunk` at a time.  To keep a long clip's video off the device
     altogether, render it through `render_motion(..., frames=(t0, t1))` and pass a generator of such pieces as `frames`."""
@@ -443,9 +444,10 @@ def save_frames(path, frames, fps=20, chunk=32):
 
     def host():
         for piece in pieces:
-            if piece.ndim != 4 or piece.shape[-1] != 3 or (piece.dtype not in (torch.uint8, np.uint8)):
-                raise ValueError(f"{what}: frames of shape {tuple(piece.shape)} and type {piece.dtype}, expected uint8 [T, H, W, 3]")
-            yield from _host_chunks(piece, chunk)
+            if piece.ndim != 4 or piece.shape[-1] not in (3, 4) or (piece.dtype not in (torch.uint8, np.uint8)):
+                raise ValueError(f"{what}: frames of shape {tuple(piece.shape)} and type {piece.dtype}, expected uint8 [T, H, W, 3 or 4]")
+            for part in _host_chunks(piece, chunk):
+                yield part[..., :3] if (part.shape[-1] == 4 and ext in (".gif", ".mp4")) else part
 
     if ext == ".npy":
         np.save(path, np.concatenate(list(host())))

@@ -92,6 +92,13 @@ class npy2obj:
     def get_vertices(self, sample_i, frame_i):
         return self.vertices[sample_i, :, :, frame_i].tolist()
 
+    def render_frames(self, **kw):
+        """The clip as video frames: `mesh_render.render_meshes` over this object's own vertices -> uint8 [1, T, H, W, 4] on the
+        device.  kw: `render_meshes`' (width, height, samples, camera, colors, frames, ...)."""
+        from .mesh_render import render_meshes
+        kw.setdefault("lengths", [self.real_num_frames])
+        return render_meshes(self.vertices.to(self.device), self.rot2xyz.smpl_model.body, **kw)
+
     def save_obj(self, save_path, frame_i):
         write_obj(save_path, self.vertices[0, :, :, frame_i].numpy(), self.faces)
         return save_path

@@ -1099,6 +1099,102 @@ int mst_render_max_traces(void);
 int mst_render_max_side(void);
 int mst_render_chunk(void);
 
+/* -----------------------------------------------------------------------------------------
+ * Meshes to video frames (csrc/mst_mesh.h): posed vertices -> [batch][frames][height][width][4] uint8 RGBA images of the shaded body
+ * over a translucent background.  Replaces the per-frame pyrender draw of `render` (visualize/render_final.py:79-89, :169-251): its
+ * scene and camera, drawn by the rules below, not by pyrender / OpenGL.  Stateless: one launch each on `stream`, nothing allocated,
+ * nothing synchronised.  No atomics; a clip's frames are the same bits alone, anywhere in a batch, on any stream and for any frame
+ * sub-range, whatever other clips or the frames behind its length hold.  Frames at and behind a clip's length are exact zeros (the
+ * face-index image: -1).  All arithmetic is float32 without fused multiply-adds, division and square root correctly rounded.
+ *
+ * mst_mesh_scene: vertices_dev element (b, t, v, c) lies at b * stride_batch + t * stride_frame + v * stride_vertex + c * stride_coord
+ * (elements; Rotation2xyz's [B][V][3][T] and [B][T][V][3] are both a choice of strides); lengths_dev [batch] int32 or NULL (every clip
+ * has `frames`), clamped to 1..frames.  faces [faces][3] int32 and the vertex -> faces adjacency in CSR form (adj_offsets
+ * [vertices + 1], adj_faces [3 faces]: the faces naming vertex v, ascending, a face once for each time it names v) are passed twice,
+ * a host copy that is checked and a device copy that the kernels read.  mst_mesh_bounds reads neither.
+ *
+ * mst_mesh_bounds (:79-80): bounds_dev [batch][8] = MINS xyz, MAXS xyz of the vertices over the clip's live frames, then two zeros.
+ * Minimum and maximum pass over NaN (fmin / fmax).
+ *
+ * mst_mesh_vertices, vertex v of frame t0 <= t < t1 of a clip, into workspace_dev (mst_mesh_workspace_bytes(batch, t1 - t0, vertices)):
+ *   Normal: n = the sum over the vertex's faces (p0, p1, p2), in adjacency order, of cross(p1 - p0, p2 - p0), each component
+ *     a * b - c * d; l = sqrt((nx nx + ny ny) + nz nz); n / l when 0 < l < inf, else n = 0.
+ *   Shade: s = ambient + (1 - ambient) max((nx lx + ny ly) + nz lz, 0); `light` is the direction towards the light, used as given.
+ *     (The reference's three directional lights (:221-229) are posed by translation only, so all three shine along -z: light (0, 0, 1);
+ *     its ambient (:197) is 0.4.)
+ *   Projection: (X, Y, Z, w) = proj (x, y, z, 1) (row-major 4 x 4: rows x, y, depth, w; proj_batch = 1 matrix for all clips or one a
+ *     clip), each row ((m0 x + m1 y) + m2 z) + m3; pixels = affine (X / w, Y / w, 1) (row-major 2 x 3), y up: pixel (row, col) covers
+ *     x in [col, col + 1], y in [height - row - 1, height - row]; depth = Z / w; 1 / w is kept.  A vertex is not drawn (all its
+ *     values NaN) when a coordinate is not finite, w is not positive and finite, or a pixel, the depth or 1 / w is not finite.
+ *   Also the pixel bounding box of the vertices drawn, one per workgroup of 256 vertices.
+ * mst_mesh_frames, from the same scene, view and workspace:
+ *   A face is never drawn when a vertex of it is not drawn or its doubled pixel area is zero or not finite.  There is no near-plane
+ *     clipping: a face with a vertex behind the camera is dropped whole.
+ *   Sample points: `samples` (1..4) a side of a pixel, sub-sample (j, i) of pixel (row, col) at x = col + (i + 0.5) / samples,
+ *     y = (height - row) - (j + 0.5) / samples; sub-sample index j * samples + i.
+ *   Coverage: the face's vertices in ascending vertex index L < M < H with pixels (xL, yL) ...; at sample (sx, sy)
+ *       wH = (xM - xL)(sy - yL) - (yM - yL)(sx - xL),  wM = -((xH - xL)(sy - yL) - (yH - yL)(sx - xL)),
+ *       wL = (xH - xM)(sy - yM) - (yH - yM)(sx - xM):
+ *     each edge function is formed from its edge's lower-index end, so two faces sharing an edge form the same number: both cover a
+ *     sample on the edge and there is no gap.  The doubled area is (xM - xL)(yH - yL) - (yM - yL)(xH - xL).  A sample is covered when
+ *     it lies inside the face's pixel bounding box (bounds included), wL, wM, wH are all >= 0 or all <= 0, and sum = (wL + wM) + wH
+ *     is not zero.
+ *   Depth: ((wL zL + wM zM) + wH zH) / sum, the screen-space barycentric mean of the vertices' depths.  The winner is the minimum of
+ *     (depth, face index) over the covering faces with a depth below +inf (NaN never wins); the face index breaks exact ties.
+ *   Shade, perspective-correct: a = w / w_clip per vertex (aL = wL (1 / w)L ...), ((aL sL + aM sM) + aH sH) / ((aL + aM) + aH).
+ *   Colour: rgb(frame) * shade composited over the background with the frame's alpha a: c = a surf + (1 - a) bg per channel, alpha
+ *     a + (1 - a) bg_a; a sample no face covers is the background (bg_r, bg_g, bg_b, bg_a).  Only the nearest surface is composited.
+ *     colors_dev [batch][frames][4] float32 RGBA per frame, or NULL: the reference's ramp (:184) for frame n of the clip,
+ *     (1, min((145 + 0.8 n) / 255, 1), min((33 + 0.5 n) / 255, 1), 0.9).  The reference's background (:169) is (1, 1, 1, 0.8).
+ *   Pixel: the sum of its sub-samples' colours in sub-sample order, divided by samples^2 last, clamped to 0..1 (NaN -> 0).
+ *     out_dev = floor(255 c + 0.5), [batch][t1 - t0][height][width][4]; out_float_dev (optional) is c itself in the same layout;
+ *     out_ids_dev (optional) int32 [batch][t1 - t0][height][width]: the winning face at sub-sample `ids_sample`, -1 for none.
+ * Refused without touching a device: a null scene, view, vertices, workspace or output, null faces, adjacency or matrix (either copy);
+ * batch outside 1..65535; frames outside 1..65535; vertices outside 1..mst_mesh_max_vertices (32768); faces outside
+ * 1..mst_mesh_max_faces (65536); a stride below 1; a face naming a vertex outside 0..vertices-1; adjacency offsets that do not run
+ * from 0 to 3 faces without falling, or an entry outside 0..faces-1; a proj_batch that is neither 1 nor batch; a matrix, affine, light,
+ * ambient or background that is not finite; width or height outside 16..mst_mesh_max_side (1024); samples outside
+ * 1..mst_mesh_max_samples (4); ids_sample outside 0..samples^2-1; a range that is not 0 <= t0 < t1 <= frames; a workspace smaller
+ * than mst_mesh_workspace_bytes says (which returns 0 for counts outside the limits); an image that is not 4-byte aligned (float
+ * image: 16); an output that is an input or another output.  mst_mesh_chunk: the faces a workgroup culls at a time (1024).
+ * ----------------------------------------------------------------------------------------- */
+typedef struct mst_mesh_scene {
+    const float* vertices_dev;
+    int64_t stride_batch, stride_frame, stride_vertex, stride_coord;
+    const int32_t* lengths_dev;
+    int32_t batch, frames, vertices, faces;
+    const int32_t* faces_host;
+    const int32_t* faces_dev;
+    const int32_t* adj_offsets_host;
+    const int32_t* adj_offsets_dev;
+    const int32_t* adj_faces_host;
+    const int32_t* adj_faces_dev;
+} mst_mesh_scene;
+typedef struct mst_mesh_view {
+    const float* proj_host;                   /* [proj_batch][16] */
+    const float* proj_dev;
+    int32_t proj_batch;
+    float affine[6];
+    int32_t width, height, samples;
+    float light[3];
+    float ambient;
+    const float* colors_dev;
+    float background[4];
+    int32_t t0, t1;
+    int32_t ids_sample;
+} mst_mesh_view;
+int mst_mesh_bounds(const mst_mesh_scene* scene_host, float* bounds_dev, void* stream);
+int mst_mesh_vertices(const mst_mesh_scene* scene_host, const mst_mesh_view* view_host, void* workspace_dev, uint64_t workspace_bytes,
+                      void* stream);
+int mst_mesh_frames(const mst_mesh_scene* scene_host, const mst_mesh_view* view_host, const void* workspace_dev, uint64_t workspace_bytes,
+                    uint8_t* out_dev, float* out_float_dev, int32_t* out_ids_dev, void* stream);
+uint64_t mst_mesh_workspace_bytes(int32_t batch, int32_t frames_out, int32_t vertices);
+int mst_mesh_max_vertices(void);
+int mst_mesh_max_faces(void);
+int mst_mesh_max_side(void);
+int mst_mesh_max_samples(void);
+int mst_mesh_chunk(void);
+
 /* Per-kernel device timing of the most recent mst_sample_loop / mst_forward when profiling is
  * enabled: HIP events recorded around every launch on the caller's stream.  names/ms are arrays
  * of `cap` entries filled with per-kernel-family totals; returns the number of families. */
